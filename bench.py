@@ -21,7 +21,18 @@ Inputs (raw sources, gains, speaker ids) are resident in HBM before the timed re
 training step starts at preprocessing + STFT.
 
   python bench.py [--gpus N] [--config C2|C4|C5] [--steps K] [--warmup W] [--precision bf16|fp32]
-                  [--mode pit|label]
+                  [--mode pit|label] [--full] [--dump-outputs DIR]
+
+A plain run sets up, warms up, times the K steps and prints the result line (``metric``, ``value``,
+``unit``, ``higher_is_better``, ``dtype``, ``ms_per_step``, the configuration and the last loss).
+``--full`` adds everything else the line can carry, each measured in runs of its own after the
+timed steps: the STFT rooflines (standalone and in-step), the two MFMA GEMM rooflines and, at one
+GPU, the CPU baselines (``--no-cpu-baseline`` / ``--no-stft-standalone`` drop those two again).
+``--dump-outputs DIR`` writes what the last timed step computed as ``DIR/<name>.npy`` (float32):
+the loss, the updated flat parameters and the flat gradient of a training step; the masks, speaker
+ids and waveforms of a recursive extraction.  Inputs and initial weights are seeded, so two builds
+run with the same arguments can be compared array for array.  Arrays that would take the dump past
+DUMP_BUDGET bytes are cut to a fixed, seeded sample of their elements (sorted flat indices).
 
 With N > 1 and no WORLD_SIZE in the environment, this process starts the N ranks itself
 (``torch.distributed.run`` as a child process, before any GPU call here) and exits with its
@@ -143,6 +154,10 @@ def parse(argv=None):
     ap.add_argument("--batch", type=int, default=None, help="per-GPU batch (default: the config's)")
     ap.add_argument("--precision", default="bf16", choices=["fp32", "bf16"])
     ap.add_argument("--mode", default="pit", choices=["label", "pit"])
+    ap.add_argument("--full", action="store_true",
+                    help="also measure the STFT / MFMA rooflines and the CPU baselines (runs of their own)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs as DIR/<name>.npy")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--eager", action="store_true",
                     help="launch every kernel of the step eagerly instead of replaying the captured HIP graph")
@@ -429,6 +444,8 @@ def standin_main(args, world, rank):
     w = torch.cat([p.detach().reshape(-1) for p in params])
     w_max = dp.max_over_ranks(float(w.sum()), "cpu", pg)
     w_min = -dp.max_over_ranks(-float(w.sum()), "cpu", pg)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {"loss": torch.tensor([loss]), "params": w})
     if rank == 0:
         print(json.dumps({"metric": "mixtures/sec (CPU stand-in step; launcher test only, not a measurement)",
                           "value": B * world * args.steps / elapsed, "unit": "mixtures/s", "n_gpus": world,
@@ -498,6 +515,23 @@ def stft_standalone(dev, N, T):
                    "stream_ceiling_source": BW_FILE + " (r1w3: one read : three write streams)"})
     del xs, Xs, Ms
     return sa
+
+
+DUMP_BUDGET = 48 << 20  # bytes of .npy data per dump (float32)
+
+
+def dump_outputs(path, arrays):
+    """Write name -> tensor as path/<name>.npy in float32.  The budget is shared in equal parts:
+    an array larger than its part is cut to a seeded sample of its flattened elements (sorted
+    indices from numpy's default_rng(0), the same for every run of the same shapes)."""
+    os.makedirs(path, exist_ok=True)
+    part = DUMP_BUDGET // (4 * len(arrays))
+    for name, t in arrays.items():
+        a = t.detach().to("cpu", torch.float32).numpy()
+        if a.size > part:
+            idx = np.sort(np.random.default_rng(0).choice(a.size, size=part, replace=False))
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(path, name + ".npy"), np.ascontiguousarray(a))
 
 
 def barrier(world):
@@ -578,7 +612,18 @@ def train_main(args, cfg, dev, world, rank, pg):
     if not np.isfinite(loss_v):
         raise RuntimeError("non-finite loss")
 
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {"loss": loss, "params": net.flat, "grad": net.grad})
+
     T = tr.T
+    if not args.full:
+        if rank == 0:
+            out = base_line(args, cfg, world, elapsed, B, T)
+            out["config"].update({"loss": args.mode, "launch": "hip-graph" if use_graph else "eager",
+                                  "step": "mix+STFT+fwd+loss+bwd+allreduce+Adam"})
+            out["loss"] = loss_v
+            print(json.dumps(out), flush=True)
+        return
     stft_ms = stft_instep_graph(tr, B, K, N)
     stft_bytes = B * (K + 1) * (4 * N + 4 * T * 129)  # mag-only STFT of mixture + K sources
     if getattr(tr, "fast", False):
@@ -720,7 +765,9 @@ def recursive_main(args, cfg, dev, world, rank, pg):
         dist.all_gather_into_tensor(gathered, mine, group=pg)
     else:
         gathered = mine
-    sa = None if args.no_stft_standalone else stft_standalone(dev, N, T)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {"masks": out["masks"], "spk": out["spk"], "waveforms": y})
+    sa = stft_standalone(dev, N, T) if args.full and not args.no_stft_standalone else None
     if rank == 0:
         g = gathered.cpu()
         line = base_line(args, cfg, world, elapsed, B, T)
@@ -731,7 +778,7 @@ def recursive_main(args, cfg, dev, world, rank, pg):
                      "gathered_extractions": int(g.shape[0]),
                      "gathered_speakers_found": int((g >= 0).sum()),
                      "speakers_row0": g[0].tolist()})
-        if not args.no_cpu_baseline and world == 1:
+        if args.full and not args.no_cpu_baseline and world == 1:
             line["cpu_baseline"] = cpu_baseline_recursive(args, cfg)
         print(json.dumps(line), flush=True)
 

@@ -2,7 +2,7 @@
 # LDS bank-conflict / MFMA-busy pass (one rocprofv3 --pmc run per variant) of a short bench run,
 # from the repo root via gpurun:  VARIANTS="base x" TAG=r04_lds bash tools/pmc_lds.sh
 R=${GRAFT_REPO_ROOT:-$(pwd)}
-BARGS=${BARGS:---steps 3 --warmup 1 --no-cpu-baseline --no-stft-standalone}
+BARGS=${BARGS:---full --steps 3 --warmup 1 --no-cpu-baseline --no-stft-standalone}
 cd /tmp && export TMPDIR=/tmp
 for v in ${VARIANTS:-base}; do
   if [ "$v" = base ]; then unset DL4SS_LIB; else export DL4SS_LIB=$R/dl4ss_amd/libdl4ss_hip_$v.so; fi

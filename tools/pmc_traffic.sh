@@ -4,7 +4,7 @@
 #   VARIANTS="base gm8" TAG=r04_pmc bash tools/pmc_traffic.sh
 # -> gpurun_out/$TAG_<variant>/pmc_{fetch,write}/run_counter_collection.csv
 R=${GRAFT_REPO_ROOT:-$(pwd)}
-BARGS=${BARGS:---steps 3 --warmup 1 --no-cpu-baseline --no-stft-standalone}
+BARGS=${BARGS:---full --steps 3 --warmup 1 --no-cpu-baseline --no-stft-standalone}
 cd /tmp && export TMPDIR=/tmp
 for v in ${VARIANTS:-base}; do
   if [ "$v" = base ]; then unset DL4SS_LIB; else export DL4SS_LIB=$R/dl4ss_amd/libdl4ss_hip_$v.so; fi

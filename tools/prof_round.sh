@@ -7,7 +7,7 @@
 #      (per launch, with its grid size: bench.py picks the launches of each measured unit)
 # Every GPU step has its own time limit; the chain stops at the first failure.
 TAG=${TAG:-prof}
-BARGS=${BARGS:---steps 3 --warmup 1 --no-cpu-baseline}
+BARGS=${BARGS:---full --steps 3 --warmup 1 --no-cpu-baseline}
 R=$GRAFT_REPO_ROOT
 mkdir -p $R/gpurun_out/$TAG
 cd /tmp && export TMPDIR=/tmp
