@@ -85,12 +85,19 @@ SIGNATURES = {
     "dl4ss_debug_set_spin_limit": [ctypes.c_uint],
     "dl4ss_debug_set_place_force": [ctypes.c_int],
     "dl4ss_debug_set_rnn_max_wg": [ctypes.c_int],
+    "dl4ss_attn_align_nblk": [I],
+    "dl4ss_attn_align_part_floats": [I, I, I],
+    "dl4ss_attn_align_fwd": [P, P, I, P, P, P, I, I, I, P, LL, P],
+    "dl4ss_attn_align_bwd": [P, P, I, P, P, P, P, I, I, I, P, P, LL, P, P, P, P, P],
+    "dl4ss_mask_attn_align_loss": [I, I, I, I, I, I, P, P, P, P, P, P, LL, P, LL, LL, P, F, F, P, P, P, LL, P, P, P],
+    "dl4ss_attn_align_finalize": [P, LL, I, I, I, I, P, P, P, P, P, P, P],
 }
 # entry points that return a value rather than a hipError_t
 RESTYPES = {"dl4ss_birnn_workspace_bytes": ctypes.c_longlong, "dl4ss_colsum_bf16_part_bytes": ctypes.c_longlong,
             "dl4ss_gemm_bf16_gl_ws_bytes": ctypes.c_longlong,
             "dl4ss_gemm_bf16_gl_grouped_ws_bytes": ctypes.c_longlong, "dl4ss_attn_nblk": ctypes.c_int,
-            "dl4ss_attn_dot_nblk": ctypes.c_int, "dl4ss_debug_set_spin_limit": None,
+            "dl4ss_attn_dot_nblk": ctypes.c_int, "dl4ss_attn_align_nblk": ctypes.c_int,
+            "dl4ss_attn_align_part_floats": ctypes.c_longlong, "dl4ss_debug_set_spin_limit": None,
             "dl4ss_debug_set_place_force": None, "dl4ss_debug_set_rnn_max_wg": None}
 
 _lib = None

@@ -229,6 +229,54 @@ class AttentionDotFn(torch.autograd.Function):
         return dV, dq, None
 
 
+def attention_align_fwd_impl(V, q, W1, W2, w3):
+    """mask (Bq,R) = sigmoid(w3 . tanh(W1 V + W2 q)): V (Bq,R,E), q (Bq,E), W1 / W2 (E,E), w3 (1,E)."""
+    V, q, W1, W2, w3 = (_c(t.float()) for t in (V, q, W1, W2, w3))
+    Bq, R, E = V.shape
+    m = torch.empty(Bq, R, device=V.device)
+    _lib.call("dl4ss_attn_align_fwd", _lib.ptr(V), _lib.ptr(q), q.shape[1], _lib.ptr(W1), _lib.ptr(W2), _lib.ptr(w3),
+              Bq, R, E, _lib.ptr(m), R, _lib.stream_ptr())
+    return m
+
+
+def attention_align_bwd_impl(dmask, V, q, W1, W2, w3, need_dV=True):
+    """(dV or None, dq, dW1, dW2, dw3) from dmask; s and the mask are recomputed from V."""
+    V, q, W1, W2, w3 = (_c(t.float()) for t in (V, q, W1, W2, w3))
+    dmask = _c(dmask.float())
+    Bq, R, E = V.shape
+    dev = V.device
+    dq, dW1, dW2, dw3 = torch.empty_like(q), torch.empty_like(W1), torch.empty_like(W2), torch.empty_like(w3)
+    if Bq == 0 or R == 0:
+        return (torch.zeros_like(V) if need_dV else None), dq.zero_(), dW1.zero_(), dW2.zero_(), dw3.zero_()
+    dV = torch.zeros_like(V) if need_dV else None
+    n = _lib.query("dl4ss_attn_align_part_floats", Bq, 1, _lib.query("dl4ss_attn_align_nblk", R))
+    part = torch.empty(n, device=dev)
+    _lib.call("dl4ss_attn_align_bwd", _lib.ptr(V), _lib.ptr(q), q.shape[1], _lib.ptr(W1), _lib.ptr(W2), _lib.ptr(w3),
+              _lib.ptr(dmask), Bq, R, E, _lib.ptr(dV), _lib.ptr(part), n, _lib.ptr(dq), _lib.ptr(dW1), _lib.ptr(dW2),
+              _lib.ptr(dw3), _lib.stream_ptr())
+    return dV, dq, dW1, dW2, dw3
+
+
+class AttentionAlignFn(torch.autograd.Function):
+    """ATTENTION 'align' (EvalVer.py:228-239; DL4SS_Keras/extend_layers.py:50-64): mask (Bq,R) =
+    sigmoid(Linear_3(tanh(Linear_1(V) + Linear_2(q)))), V (Bq,R,E), q (Bq,E), the three bias-free
+    Linear weights W1 (E,E), W2 (E,E), w3 (1,E)."""
+
+    @staticmethod
+    def forward(ctx, V, q, W1, W2, w3):
+        V, q, W1, W2, w3 = (_c(t.float()) for t in (V, q, W1, W2, w3))
+        ctx.save_for_backward(V, q, W1, W2, w3)
+        return attention_align_fwd_impl(V, q, W1, W2, w3)
+
+    @staticmethod
+    def backward(ctx, dmask):
+        V, q, W1, W2, w3 = ctx.saved_tensors
+        need = ctx.needs_input_grad
+        dV, dq, dW1, dW2, dw3 = attention_align_bwd_impl(dmask, V, q, W1, W2, w3, bool(need[0]))
+        return (dV, dq if need[1] else None, dW1 if need[2] else None, dW2 if need[3] else None,
+                dw3 if need[4] else None)
+
+
 class EmbeddingGatherFn(torch.autograd.Function):
     """q (B,K,W) = Emb[idx]: SPEECH_EMBEDDING gather (EvalVer.py:355-360)."""
 

@@ -5,7 +5,9 @@ The reference saves one ``state_dict`` per module every 5 epochs
 (``TDAA_beta/main_run_sstune_EvalVer.py:677-690``: ``..._hidden3d_{epoch}`` = MIX_SPEECH,
 ``_emblayer_`` = SPEECH_EMBEDDING, ``_adjlayer_`` = ADDJUST, ``_attlayer_`` = ATTENTION,
 ``_dislayer_`` = Discriminator) and loads them back the same way (``EvalVer.py:545-554``;
-the classifier file drops its ``cnn`` keys, ``:547-549``).  Key names inside each file are
+the classifier file drops its ``cnn`` keys, ``:547-549``).  The ``_attlayer_`` file is read
+and written for nets with the 'align' attention (``SepNet(attention="align")``), whose three
+weights it holds; a 'dot' net has none of them.  Key names inside each file are
 the module's own: ``layer.weight_ih_l0[_reverse]`` / ``Linear.weight`` (MIX_SPEECH),
 ``layer.weight`` (embedding, ADDJUST), ``Linear_{1,2,3}.weight`` (attention).
 
@@ -23,7 +25,7 @@ import os
 
 import torch
 
-PREFIX = {"hidden3d": "mix.", "emblayer": "emb.", "adjlayer": "adj."}
+PREFIX = {"hidden3d": "mix.", "emblayer": "emb.", "adjlayer": "adj.", "attlayer": "att."}
 
 
 def load_state(path):
@@ -33,13 +35,16 @@ def load_state(path):
     return {k: (v.data if hasattr(v, "data") else v) for k, v in sd.items()}
 
 
-def load_reference_params(net, hidden3d=None, emblayer=None, adjlayer=None, strict=True):
+def load_reference_params(net, hidden3d=None, emblayer=None, adjlayer=None, strict=True, attlayer=None):
     """Load the reference's per-module files into a SepNet (in place).  Missing module files
     are skipped; with ``strict`` every key of a given file must map onto the net AND every
     parameter of the net under that file's module prefix must be in the file (torch's
     ``load_state_dict(strict=True)`` in both directions: a 2-layer hidden3d file does not
-    silently leave layers 2-3 of a 4-layer net at their random init)."""
-    for kind, path in (("hidden3d", hidden3d), ("emblayer", emblayer), ("adjlayer", adjlayer)):
+    silently leave layers 2-3 of a 4-layer net at their random init).  ``attlayer`` is the
+    ATTENTION file (``Linear_{1,2,3}.weight``), for a net built with ``attention="align"``; a
+    'dot' net has no counterpart for its keys, so a strict load of it raises."""
+    for kind, path in (("hidden3d", hidden3d), ("emblayer", emblayer), ("adjlayer", adjlayer),
+                       ("attlayer", attlayer)):
         if path is None:
             continue
         sd = load_state(path)
@@ -81,7 +86,8 @@ def load_reference_classifier(cnet, path, strict=True):
 
 
 def save_reference_params(net, directory, tag, epoch):
-    """Write the reference's file layout ``param_{tag}_{hidden3d,emblayer,adjlayer}_{epoch}``."""
+    """Write the reference's file layout ``param_{tag}_{hidden3d,emblayer,adjlayer}_{epoch}``, and
+    ``param_{tag}_attlayer_{epoch}`` for a net that has the 'align' attention weights."""
     os.makedirs(directory, exist_ok=True)
     paths = {}
     for kind, pre in PREFIX.items():

@@ -12,7 +12,7 @@ reference ``state_dict`` keys load unchanged) and forward semantics follow:
   SPEECH_EMBEDDING       main_run.py:307-327 (dense, masked), EvalVer.py:348-361 (gather),
                          cRM:390-406 (width 2E)
   ADDJUST                EvalVer.py:363-377, cRM:408-426
-  ATTENTION              EvalVer.py:199-242 ('dot'), cRM:247-271 (cRM 'dot' branch)
+  ATTENTION              EvalVer.py:199-242 ('dot' and 'align'), cRM:247-271 (cRM 'dot' branch)
   top_k_mask             main_run.py:340-355, EvalVer.py:390-405
 
 Forward and backward of the recurrence, every Linear / GEMM, the attention, the
@@ -171,8 +171,10 @@ class ADDJUST(nn.Module):
 class ATTENTION(nn.Module):
     """'dot' mode on the HIP kernel: mask = sigmoid(V . q) (EvalVer.py:216-226); with
     config.is_ComlexMask the cRM branch 10 tanh(V . q_half), (B', T, F, 2) (cRM:259-271).
-    'align' keeps its parameters (state_dict compatibility) but is never executed by the
-    reference and raises."""
+    'align' (EvalVer.py:228-239; DL4SS_Keras/extend_layers.py:50-64): additive attention
+    sigmoid(Linear_3(tanh(Linear_1(mix_hidden) + Linear_2(query)))) on its own three bias-free
+    Linears, (B', T, F), on the HIP kernel too.  'align' with the cRM flag is a pair the
+    reference never ran and raises."""
 
     def __init__(self, hidden_size, mode='dot', crm=None):
         super().__init__()
@@ -184,12 +186,18 @@ class ATTENTION(nn.Module):
         self.Linear_3 = nn.Linear(hidden_size, 1, bias=False)
 
     def forward(self, mix_hidden, query):
-        if self.mode != 'dot':
-            raise NotImplementedError("ATTENTION 'align' is constructed but never run by the reference")
+        if self.mode not in ('dot', 'align'):
+            raise NotImplementedError(f"ATTENTION mode {self.mode!r}: the reference defines 'dot' and 'align'")
+        if self.mode == 'align' and self.crm:
+            raise NotImplementedError("ATTENTION 'align' with the complex ratio mask (is_ComlexMask): the "
+                                      "reference never ran this pair; use mode='dot' for cRM")
         B = mix_hidden.shape[0]
         shp = mix_hidden.shape
         V = mix_hidden.reshape(B, -1, self.hidden_size)
         q = query.reshape(B, -1)
+        if self.mode == 'align':
+            mask = ag.AttentionAlignFn.apply(V, q, self.Linear_1.weight, self.Linear_2.weight, self.Linear_3.weight)
+            return mask.view(B, shp[1], shp[2])
         mask = ag.AttentionDotFn.apply(V, q, self.crm)
         return mask.view(B, shp[1], shp[2], 2) if self.crm else mask.view(B, shp[1], shp[2])
 

@@ -3,8 +3,9 @@
 LR-halving lines ``for ee in optimizer.param_groups: ee['lr'] /= 2`` work unchanged,
 EvalVer.py:570-575), ``zero_grad`` and ``step`` -- with the update on the HIP Adam kernel
 (dl4ss_adam: torch's Adam arithmetic, bias corrections in double on the host), one launch
-per parameter.  Parameters without a gradient (the discarded classifier, the unused
-'align' attention weights) are skipped, as torch skips them.
+per parameter.  Parameters without a gradient (the discarded classifier; the Linear_1/2/3
+weights of an ATTENTION run in 'dot' mode, which only 'align' mode uses and trains) are
+skipped, as torch skips them.
 """
 import torch
 

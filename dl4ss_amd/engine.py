@@ -41,7 +41,14 @@ class SepNet:
     """Trainable parameters of the mask network, flat fp32 with named views."""
 
     def __init__(self, cell="lstm", num_layers=4, hidden=300, emb=50, num_labels=101, input_fre=129, crm=False,
-                 adjust=True, device="cuda", seed=1):
+                 adjust=True, device="cuda", seed=1, attention="dot"):
+        if attention not in ("dot", "align"):
+            raise ValueError(f"attention={attention!r}: expected 'dot' or 'align'")
+        if attention == "align" and crm:
+            raise ValueError("attention='align' with a cRM net is unsupported (the reference never ran that pair)")
+        # 'dot': mask = sigmoid(V . q); 'align': sigmoid(w3 . tanh(W1 V + W2 q)) on the three extra
+        # ATTENTION weights (EvalVer.py:228-239; DL4SS_Keras/extend_layers.py:50-64)
+        self.attention = attention
         self.cell, self.L, self.H, self.E = cell, num_layers, hidden, emb
         self.F, self.num_labels, self.crm, self.adjust = input_fre, num_labels, crm, adjust
         self.W = 2 * emb if crm else emb
@@ -57,6 +64,9 @@ class SepNet:
                   ("emb.layer.weight", (num_labels, self.W))]
         if adjust:
             specs.append(("adj.layer.weight", (self.W, 2 * hidden + self.W)))
+        if attention == "align":  # behind every 'dot' parameter: the default layout does not move
+            specs += [("att.Linear_1.weight", (emb, emb)), ("att.Linear_2.weight", (emb, emb)),
+                      ("att.Linear_3.weight", (1, emb))]
         self.specs = specs
         self.offsets = {}
         off = 0
@@ -102,7 +112,7 @@ class SepNet:
     def bucket_split(self):
         """Index into grad_ext between the data-parallel buckets: [0, split) = the status flag and
         every recurrent layer (complete after the last BPTT), [split, end) = the Linear, the speaker
-        embedding and ADDJUST (complete before the first BPTT)."""
+        embedding, ADDJUST and the 'align' attention weights (complete before the first BPTT)."""
         return 4 + self.offsets["mix.Linear.weight"][0]
 
     def bucket_mid(self, layer):
@@ -147,8 +157,23 @@ class SepTrainer:
             raise ValueError(mode)
         if (mode == "crm") != net.crm:
             raise ValueError("cRM mode needs a cRM net (query width 2E) and vice versa")
+        self.align = getattr(net, "attention", "dot") == "align"
+        if self.align:
+            if mode == "crm":
+                raise ValueError("attention='align' supports the modes 'label' and 'pit', not 'crm'")
+            if loss_channels:
+                raise ValueError("attention='align' does not support loss_channels")
+            if precision in ("bf16s", "bf16s2") or (precision == "bf16" and (rnn_precision or precision) == "bf16"):
+                raise ValueError(f"attention='align' is not built for the bf16 / bf16s fast paths "
+                                 f"(precision={precision!r}, rnn_precision={rnn_precision!r}); use precision='fp32'")
+            if net.E != 50:
+                raise ValueError("attention='align' is built for embedding size 50")
         self.net, self.B, self.K, self.N = net, batch, k, n_samples
         self.mode, self.precision = mode, precision
+        # split-K of the fp32 step's backward GEMMs (gemm.hip: fp32 atomics, the order of the partial sums
+        # varies from launch to launch).  The 'align' step keeps every GEMM in one piece instead, so that its
+        # gradients are bitwise reproducible, eager or replayed
+        self._sk = 1 if self.align else "auto"
         # recurrent matvec precision (defaults to the GEMM precision): "fp32" exact VALU,
         # "bf16" MFMA with fp32 accumulate and fp32 cell state
         self.rnn_precision = rnn_precision or precision
@@ -193,9 +218,11 @@ class SepTrainer:
         self.mean = torch.empty(B, 2 * H, **f32)
         self.dq = torch.empty(B, K, W, **f32)
         self.dh_bcast = torch.empty(B, 2 * H, **f32)
-        self.nblk = _lib.query("dl4ss_attn_nblk", T, F)
+        self.nblk = _lib.query("dl4ss_attn_align_nblk", T * F) if self.align else _lib.query("dl4ss_attn_nblk", T, F)
         self.part_loss = torch.empty(B, self.nblk, K * K + 1, **f32)
         self.part_dq = torch.empty(B, self.nblk, K, W, **f32)
+        if self.align:  # the align GRAD pass's partial records (dW1, dp, dw3 per block) + finalize scratch
+            self.part_att = torch.empty(_lib.query("dl4ss_attn_align_part_floats", B, K, self.nblk), **f32)
         self.perm = torch.empty(B, K, device=dev, dtype=torch.int32)
         self.loss = torch.zeros(3, **f32)
         ws = _lib.query("dl4ss_birnn_workspace_bytes", CELLS[net.cell], B, H)
@@ -614,6 +641,16 @@ class SepTrainer:
     def attn(self, pass_, perm=None, mask_out=None, pred_out=None):
         X, xs, Y, ys, yks = self._attn_args()
         grad = pass_ == 1
+        if self.align:
+            net = self.net
+            _lib.call("dl4ss_mask_attn_align_loss", pass_, self.B, self.K, self.T, self.F, net.E, _lib.ptr(self.V),
+                      _lib.ptr(self.q), _lib.ptr(net.view("att.Linear_1.weight")),
+                      _lib.ptr(net.view("att.Linear_2.weight")), _lib.ptr(net.view("att.Linear_3.weight")),
+                      _lib.ptr(X), xs, _lib.ptr(Y), ys, yks, _lib.ptr(perm), self.s1, self.s2,
+                      _lib.ptr(self.V) if grad else None, _lib.ptr(self.part_loss),
+                      _lib.ptr(self.part_att) if grad else None, self.part_att.numel(), _lib.ptr(mask_out),
+                      _lib.ptr(pred_out), _lib.stream_ptr())
+            return
         dpre = _lib.ptr(self.V) if grad and not self.fast else None
         # (the COST pass gets dPre_bf16 too: it selects the same attention kernel as the GRAD pass)
         dpreb = _lib.ptr(self.dPreb) if self.fast else None
@@ -635,6 +672,18 @@ class SepTrainer:
             _lib.call("dl4ss_pit_select", _lib.ptr(self.part_loss), self.B, self.K, self.nblk, _lib.ptr(self.perm), st)
             perm = self.perm
         self.attn(1, perm)
+        if self.align:
+            # the loss from the same partials; dq and the three attention-weight gradients from the align
+            # partials, straight into their views of the flat gradient (backward_early zeroes only the
+            # range in front of them)
+            net, g = self.net, self.net.grad
+            _lib.call("dl4ss_loss_finalize", _lib.ptr(self.part_loss), self.B, self.K, self.nblk, _lib.ptr(perm),
+                      self.s1, self.s2, _lib.ptr(self.loss), None, net.W, None, st)
+            _lib.call("dl4ss_attn_align_finalize", _lib.ptr(self.part_att), self.part_att.numel(), self.B, self.K,
+                      self.T, self.F, _lib.ptr(self.q), _lib.ptr(net.view("att.Linear_2.weight")), _lib.ptr(self.dq),
+                      _lib.ptr(net.view("att.Linear_1.weight", g)), _lib.ptr(net.view("att.Linear_2.weight", g)),
+                      _lib.ptr(net.view("att.Linear_3.weight", g)), st)
+            return self.loss
         _lib.call("dl4ss_loss_finalize", _lib.ptr(self.part_loss), self.B, self.K, self.nblk, _lib.ptr(perm),
                   self.s1, self.s2, _lib.ptr(self.loss), _lib.ptr(self.part_dq), self.net.W, _lib.ptr(self.dq), st)
         return self.loss
@@ -874,7 +923,9 @@ class SepTrainer:
         net, B, T, H = self.net, self.B, self.T, self.net.H
         BT = B * T
         g = net.grad
-        if not self.zero_free:
+        if self.align:  # the attention-weight gradients behind this range were written by loss_and_grad
+            g[:net.offsets["att.Linear_1.weight"][0]].zero_()
+        elif not self.zero_free:
             g.zero_()
         self._query_bwd()
         if self.fast:
@@ -883,10 +934,10 @@ class SepTrainer:
         dPre = self.V
         hL = self.out[-1].view(BT, 2 * H)
         # grads were zeroed above: weight gradients accumulate (beta 1) with split-K
-        ops.gemm(dPre, hL, transA=True, out=net.view("mix.Linear.weight", g), beta=1.0, splitk="auto",
+        ops.gemm(dPre, hL, transA=True, out=net.view("mix.Linear.weight", g), beta=1.0, splitk=self._sk,
                  precision=self.precision)
         ops.colsum(dPre, net.view("mix.Linear.bias", g))
-        ops.gemm(dPre, net.view("mix.Linear.weight"), out=self.dH[0], splitk="auto", precision=self.precision)
+        ops.gemm(dPre, net.view("mix.Linear.weight"), out=self.dH[0], splitk=self._sk, precision=self.precision)
 
     def _query_bwd(self):
         """SPEECH_EMBEDDING / ADDJUST backward: the embedding and ADDJUST gradients (added into the
@@ -924,18 +975,18 @@ class SepTrainer:
                       _lib.ptr(self.dGh) if self.dGh is not None else None, _lib.ptr(self.rnn_ws), self.ws_bytes,
                       _lib.ptr(self.status), st)
             xl = self.mag_mix.view(BT, -1) if l == 0 else self.out[l - 1].view(BT, 2 * H)
-            ops.gemm(dG, xl, transA=True, out=net.cat_view("weight_ih", l, g), splitk="auto", beta=1.0,
+            ops.gemm(dG, xl, transA=True, out=net.cat_view("weight_ih", l, g), splitk=self._sk, beta=1.0,
                      precision=self.precision)
             ops.colsum(dG, net.cat_view("bias_ih", l, g))
             whh_g = net.cat_view("weight_hh", l, g)
             hp = self.hprev[l].view(BT, 2 * H)
             for d in range(2):
                 ops.gemm(dGh[:, d * NGH:(d + 1) * NGH], hp[:, d * H:(d + 1) * H], transA=True,
-                         out=whh_g[d * NGH:(d + 1) * NGH], splitk="auto", beta=1.0, precision=self.precision)
+                         out=whh_g[d * NGH:(d + 1) * NGH], splitk=self._sk, beta=1.0, precision=self.precision)
             ops.colsum(dGh, net.cat_view("bias_hh", l, g))
             if l > 0:
                 dH_next = self.dH[1] if dH is self.dH[0] else self.dH[0]
-                ops.gemm(dG, net.cat_view("weight_ih", l), out=dH_next, splitk="auto", precision=self.precision)
+                ops.gemm(dG, net.cat_view("weight_ih", l), out=dH_next, splitk=self._sk, precision=self.precision)
                 dH = dH_next
         self._status_flag()
 

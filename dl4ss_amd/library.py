@@ -24,6 +24,8 @@ conj)``                                cRM_EvalVer.py:96-99,720-728)
 w_hh, b_hh, cell, H, precision)``      main_run.py:263-273); returns (out, hprev, act, cs)
 ``dl4ss::linear_tanh(x, w, b, prec)``  MIX_SPEECH head tanh(Linear) (EvalVer.py:290,298-299)
 ``dl4ss::attention_dot(V, q, crm)``    ATTENTION 'dot' mask (EvalVer.py:216-226, cRM:259-271)
+``dl4ss::attention_align(V, q, W1,     ATTENTION 'align' mask (EvalVer.py:228-239,
+W2, w3)``                              DL4SS_Keras/extend_layers.py:50-64)
 ``dl4ss::top_k_mask(p, alpha, k)``     top_k_mask (EvalVer.py:390-405)
 =====================================  ==========================================================
 
@@ -247,6 +249,46 @@ def _att_backward(ctx, dmask):
 attention_dot.register_autograd(_att_backward, setup_context=_att_setup)
 
 
+# --------------------------------------------------------------------------- ATTENTION 'align'
+@_op("attention_align")
+def attention_align(V: Tensor, q: Tensor, W1: Tensor, W2: Tensor, w3: Tensor) -> Tensor:
+    return ag.attention_align_fwd_impl(V, q, W1, W2, w3)
+
+
+@attention_align.register_fake
+def _(V, q, W1, W2, w3):
+    Bq, R, _ = V.shape
+    return V.new_empty(Bq, R, **F32)
+
+
+@_op("attention_align_bwd")
+def attention_align_bwd(dmask: Tensor, V: Tensor, q: Tensor, W1: Tensor, W2: Tensor, w3: Tensor,
+                        need_dV: bool) -> Tuple[Tensor, Tensor, Tensor, Tensor, Tensor]:
+    dV, dq, dW1, dW2, dw3 = ag.attention_align_bwd_impl(dmask, V, q, W1, W2, w3, need_dV)
+    return (dV if dV is not None else V.new_empty(0)), dq, dW1, dW2, dw3
+
+
+@attention_align_bwd.register_fake
+def _(dmask, V, q, W1, W2, w3, need_dV):
+    return ((torch.empty_like(V, **F32) if need_dV else V.new_empty(0, **F32)), torch.empty_like(q, **F32),
+            torch.empty_like(W1, **F32), torch.empty_like(W2, **F32), torch.empty_like(w3, **F32))
+
+
+def _align_setup(ctx, inputs, output):
+    ctx.save_for_backward(*inputs)
+
+
+def _align_backward(ctx, dmask):
+    V, q, W1, W2, w3 = ctx.saved_tensors
+    need = ctx.needs_input_grad
+    dV, dq, dW1, dW2, dw3 = attention_align_bwd(dmask.contiguous(), V, q, W1, W2, w3, bool(need[0]))
+    return (dV if need[0] else None, dq if need[1] else None, dW1 if need[2] else None, dW2 if need[3] else None,
+            dw3 if need[4] else None)
+
+
+attention_align.register_autograd(_align_backward, setup_context=_align_setup)
+
+
 # --------------------------------------------------------------------------- top-k speaker mask
 @_op("top_k_mask")
 def top_k_mask(prob: Tensor, alpha: float, top_k: int) -> Tuple[Tensor, Tensor, Tensor]:
@@ -262,4 +304,5 @@ def _(prob, alpha, top_k):
 
 
 OPS = ("stft_mag", "stft_complex", "istft", "istft_apply", "mix_sources", "birnn_layer", "birnn_layer_bwd",
-       "linear_tanh", "linear_tanh_bwd", "attention_dot", "attention_dot_bwd", "top_k_mask")
+       "linear_tanh", "linear_tanh_bwd", "attention_dot", "attention_dot_bwd", "attention_align",
+       "attention_align_bwd", "top_k_mask")

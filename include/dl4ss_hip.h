@@ -401,6 +401,43 @@ int dl4ss_top_k_mask(const float* prob, int B, int N, float alpha, int top_k, fl
 int dl4ss_attn_dot_fwd_ex(const float* V, const float* q, int q_stride, int Bq, int R, int E, int act, float* mask,
                           long long mask_stride, void* stream);
 
+/* ---- ATTENTION 'align' (additive attention) ---- */
+/* mask = sigmoid(w3 . tanh(W1 V + W2 q)): Cocktail/software/DL4SS_Keras/extend_layers.py:50-64
+ * (built by default, nnet.py:88) and the 'align' branch of the Torch ATTENTION classes
+ * (TDAA_beta/main_run_sstune_EvalVer.py:228-239).  W1 = Linear_1.weight (E,E), W2 =
+ * Linear_2.weight (E,E), w3 = Linear_3.weight (1,E), no biases; E = 50 only. */
+/* Blocks per utterance of R rows (part_loss is (B, nblk, K*K+1) as for dl4ss_mask_attn_loss). */
+int dl4ss_attn_align_nblk(int R);
+/* Floats of the backward's partial-sum workspace `part` for B utterances of nblk blocks and K
+ * queries each (the module-level backward: B = Bq, K = 1); -1 for an unsupported K. */
+long long dl4ss_attn_align_part_floats(int B, int K, int nblk);
+/* Module level, forward: mask[b * mask_stride + r], V (Bq,R,E), the query of b at q + b * q_stride
+ * (K queries of one V write a (B,K,R) mask with mask_stride = K*R, as dl4ss_attn_dot_fwd_ex). */
+int dl4ss_attn_align_fwd(const float* V, const float* q, int q_stride, const float* W1, const float* W2,
+                         const float* w3, int Bq, int R, int E, float* mask, long long mask_stride, void* stream);
+/* Its backward from dmask (Bq,R), s and the mask recomputed from V: dV (Bq,R,E) += dU W1 (may be
+ * NULL), and dq (Bq,E), dW1, dW2, dw3 written.  Per-block partials in `part` (part_floats >=
+ * dl4ss_attn_align_part_floats(Bq, 1, dl4ss_attn_align_nblk(R))), summed in fixed order: no atomics. */
+int dl4ss_attn_align_bwd(const float* V, const float* q, int q_stride, const float* W1, const float* W2,
+                         const float* w3, const float* dmask, int Bq, int R, int E, float* dV, float* part,
+                         long long part_floats, float* dq, float* dW1, float* dW2, float* dw3, void* stream);
+/* The fused step kernel, the 'align' counterpart of dl4ss_mask_attn_loss on fp32 V (magnitude path;
+ * the loss of EvalVer.py:641,659-666): pass 0 COST, pass 1 GRAD, with that entry point's V / q (B,K,E)
+ * / X / Y / strides / perm / s1 / s2 / mask_out / pred_out contract; part_loss (B,nblk,K*K+1), nblk =
+ * dl4ss_attn_align_nblk(T*F), feeds dl4ss_pit_select and dl4ss_loss_finalize (with dq NULL) unchanged.
+ * GRAD writes dPre (B,T*F,E) (may be V itself: in place) and the partials of dp, dW1, dw3 into `part`
+ * (part_floats >= dl4ss_attn_align_part_floats(B, K, nblk)); dl4ss_attn_align_finalize forms the
+ * gradients from them. */
+int dl4ss_mask_attn_align_loss(int pass, int B, int K, int T, int F, int E, const float* V, const float* q,
+                               const float* W1, const float* W2, const float* w3, const float* X,
+                               long long x_bstride, const float* Y, long long y_bstride, long long y_kstride,
+                               const int* perm, float s1, float s2, float* dPre, float* part_loss, float* part,
+                               long long part_floats, float* mask_out, float* pred_out, void* stream);
+/* dq (B,K,E), dW1 (E,E), dW2 (E,E), dw3 (E), written, from the GRAD pass's `part` (q, W2 as given
+ * to it): the block partials summed in block order, dq = dp W2, dW2 = sum_{b,k} dp (x) q. */
+int dl4ss_attn_align_finalize(const float* part, long long part_floats, int B, int K, int T, int F, const float* q,
+                              const float* W2, float* dq, float* dW1, float* dW2, float* dw3, void* stream);
+
 /* ---- recursive extraction / speaker classifier ---- */
 /* Speaker choice of one recursion step (Torch_multi/main_run_multi_selfSS_recuReal_GRID.py:
  * 227-244 top_k_mask with sort_index, 391-404 the seen-speaker filter), per row b:
