@@ -91,6 +91,8 @@ SIGNATURES = {
     "dl4ss_attn_align_bwd": [P, P, I, P, P, P, P, I, I, I, P, P, LL, P, P, P, P, P],
     "dl4ss_mask_attn_align_loss": [I, I, I, I, I, I, P, P, P, P, P, P, LL, P, LL, LL, P, F, F, P, P, P, LL, P, P, P],
     "dl4ss_attn_align_finalize": [P, LL, I, I, I, I, P, P, P, P, P, P, P],
+    "dl4ss_cls_head_fwd": [P, P, P, I, I, I, P, P, P],
+    "dl4ss_cls_head_loss_bwd": [P, P, P, P, I, I, I, I, P, P, P, P, P, P],
 }
 # entry points that return a value rather than a hipError_t
 RESTYPES = {"dl4ss_birnn_workspace_bytes": ctypes.c_longlong, "dl4ss_colsum_bf16_part_bytes": ctypes.c_longlong,

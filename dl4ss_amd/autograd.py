@@ -15,6 +15,7 @@ import torch
 from . import _lib, ops
 
 CELLS = {"lstm": 0, "gru": 1}
+LARGE_H = 320  # hidden sizes above it run dl4ss_birnn_bwd_ex's large-hidden BPTT (up to 640)
 
 
 def _c(t):
@@ -67,10 +68,14 @@ def birnn_bwd_impl(dout, x, w_ih, w_hh, hprev, act, cs, cell, H, precision, need
     dGh = torch.empty_like(dG) if cell == "gru" else None
     ws = torch.empty((wsn + 7) // 8, dtype=torch.int64, device=dev)
     status = torch.zeros(1, dtype=torch.int32, device=dev)
-    _lib.call("dl4ss_birnn_bwd", CELLS[cell], ops.PREC[precision], B, T, H, _lib.ptr(dout), None,
-              _lib.ptr(_c(w_hh)), _lib.ptr(act), _lib.ptr(cs) if cell == "lstm" else None, _lib.ptr(hprev),
-              _lib.ptr(dG), _lib.ptr(dGh) if dGh is not None else None, _lib.ptr(ws), wsn, _lib.ptr(status),
-              _lib.stream_ptr())
+    bptt = (CELLS[cell], ops.PREC[precision], B, T, H, _lib.ptr(dout), None, _lib.ptr(_c(w_hh)), _lib.ptr(act),
+            _lib.ptr(cs) if cell == "lstm" else None, _lib.ptr(hprev), _lib.ptr(dG),
+            _lib.ptr(dGh) if dGh is not None else None)
+    if H > LARGE_H:  # the H = 600 classifier: the large-hidden BPTT (generic kernel, no bf16 extras)
+        _lib.call("dl4ss_birnn_bwd_ex", *bptt, None, None, None, None, _lib.ptr(ws), wsn, _lib.ptr(status),
+                  _lib.stream_ptr())
+    else:
+        _lib.call("dl4ss_birnn_bwd", *bptt, _lib.ptr(ws), wsn, _lib.ptr(status), _lib.stream_ptr())
     _check_status(status, "dl4ss_birnn_bwd")
     dGh = dG if dGh is None else dGh
     w_ih = _c(w_ih)

@@ -85,6 +85,17 @@ def load_reference_classifier(cnet, path, strict=True):
     return cnet
 
 
+def save_reference_classifier(cnet, path):
+    """A ClassifierNet as the reference saves its classifier (test_multi_labels_speech.py:447-449): one
+    plain state_dict with the module's own keys (``layer.*`` / ``Linear.*``) on the CPU.  Round-trips
+    through ``load_reference_classifier``; the driver mirrors' ``load_params(classifier=path)`` load it."""
+    d = os.path.dirname(path)
+    if d:
+        os.makedirs(d, exist_ok=True)
+    torch.save({name: cnet.view(name).detach().cpu().clone() for name, _ in cnet.specs}, path)
+    return path
+
+
 def save_reference_params(net, directory, tag, epoch):
     """Write the reference's file layout ``param_{tag}_{hidden3d,emblayer,adjlayer}_{epoch}``, and
     ``param_{tag}_attlayer_{epoch}`` for a net that has the 'align' attention weights."""

@@ -1,0 +1,173 @@
+"""Training step of the speaker classifier on the HIP kernels.
+
+``MIX_SPEECH_classifier`` (BiLSTM(129, 600, 3 layers) -> mean over t -> Linear(1200, N_lab) -> sigmoid,
+``Torch_multi/test_multi_labels_speech.py:240-263``) is trained by the reference with
+``nn.MultiLabelSoftMarginLoss`` on the sigmoid output and Adam (``:389-445``); ``ClassifierTrainer`` is that
+step on a ``ClassifierNet`` (``dl4ss_amd.infer``), whose weights the inference paths then read directly
+(``ClassifierForward``, ``RecursiveExtractor``, the drivers' ``load_params(classifier=...)``).
+
+Per step: mixing + STFT magnitude kernels (``features``), per layer the input-projection GEMM and the
+persistent recurrence with its saved ``out / hprev / act / cs`` (``forward``), ``dl4ss_time_mean`` and the
+head kernels of ``cls_head.hip`` (``loss_and_grad``), then top-down the large-hidden BPTT
+(``dl4ss_birnn_bwd_ex``; the top layer takes only the head's ``dOut_bcast``) with the weight / bias / input
+gradient GEMMs unsplit, so a step on B * T <= 256 rows is reproducible bit for bit (``backward``), and the
+guarded Adam (``optimizer_step``).  Single GPU, eager launches (no HIP-graph capture).
+"""
+import torch
+
+from . import _lib, ops
+
+LSTM = 0
+
+
+class ClassifierTrainer:
+    """``precision``: "fp32" -- fp32 GEMMs, exact fp32 recurrence (precision 0); "bf16" -- bf16 GEMM
+    operands, bf16 MFMA recurrent matvec (precision 1), fp32 accumulate and state everywhere.
+    ``lr``: what the reference's optimizer is built with (1e-5, ``:395``); ``schedule.classifier()`` halves
+    it from epoch 0 on."""
+
+    def __init__(self, cnet, batch, k, n_samples, precision="fp32", lr=1e-5, betas=(0.9, 0.999), eps=1e-8):
+        if precision not in ops.PREC:
+            raise ValueError(f"precision {precision!r}: expected one of {sorted(ops.PREC)}")
+        self.net, self.B, self.K, self.N = cnet, batch, k, n_samples
+        self.precision = precision
+        self.lr, self.betas, self.eps = lr, betas, eps
+        B, K, N, H, L, C = batch, k, n_samples, cnet.H, cnet.L, cnet.num_labels
+        self.T = T = ops.n_frames(n_samples)
+        self.F = F = cnet.F
+        dev = cnet.device
+        f32 = dict(device=dev, dtype=torch.float32)
+        self._sig = torch.empty(B + B * K, N, **f32)  # [mixtures | sources]: the mixing kernel's outputs
+        self.mix = self._sig[:B]
+        self.src = self._sig[B:].view(B, K, N)
+        self.stats = torch.empty(32 * B * K, **f32)
+        self.feats = torch.empty(B, T, F, **f32)
+        self.G = torch.empty(B * T, 2 * 4 * H, **f32)  # input projections, then dG of the same layer
+        self.out = [torch.empty(B, T, 2 * H, **f32) for _ in range(L)]
+        self.hprev = [torch.empty(B, T, 2 * H, **f32) for _ in range(L)]
+        self.act = [torch.empty(B, T, 2, 4 * H, **f32) for _ in range(L)]
+        self.cs = [torch.empty(B, T, 2, H, **f32) for _ in range(L)]
+        self.dH = [torch.empty(B * T, 2 * H, **f32) for _ in range(min(2, L - 1))]
+        self.mean = torch.empty(B, 2 * H, **f32)
+        self.logits = torch.empty(B, C, **f32)
+        self.prob = torch.empty(B, C, **f32)
+        self.y = torch.zeros(B, C, **f32)
+        self.dz = torch.empty(B, C, **f32)
+        self.dmb = torch.empty(B, 2 * H, **f32)  # d(mean_t h) / T: the top BPTT's dOut_bcast
+        # the top layer's dOut is identically zero: NULL for the generic BPTT kernel; the packed bf16
+        # kernels of the small nets (H <= 320) read a dOut, a zero buffer that nothing writes
+        self._zero_dout = torch.zeros(B * T, 2 * H, **f32) if (precision == "bf16" and H <= 320) else None
+        self.loss = torch.zeros(1, **f32)
+        ws = _lib.query("dl4ss_birnn_workspace_bytes", LSTM, B, H)
+        if ws < 0:
+            raise RuntimeError(f"BiRNN shape unsupported (B={B}, H={H})")
+        self.ws_bytes = ws
+        self.rnn_ws = torch.zeros((ws + 7) // 8, device=dev, dtype=torch.int64)
+        self.status = torch.zeros(2, device=dev, dtype=torch.int32)  # {hand-off timed out, refused updates}
+        cnet.grad = torch.zeros_like(cnet.flat)
+        self.m = torch.zeros_like(cnet.flat)
+        self.v = torch.zeros_like(cnet.flat)
+        self.step_count = 0
+
+    # ------------------------------------------------------------------ features
+    def features(self, raw=None, gains=None, feats=None):
+        """raw (B, K, N) sources + gains (B, K) -> |STFT| of the mixtures (B, T, F); or precomputed
+        ``feats`` (B, T, F)."""
+        if feats is not None:
+            self.feats.copy_(feats)
+            return self.feats
+        ops.mix_sources(raw, gains, out_src=self.src, out_mix=self.mix, stats_ws=self.stats)
+        ops.stft(self.mix, complex_out=False, mag_out=True, out_mag=self.feats)
+        return self.feats
+
+    # ------------------------------------------------------------------ forward
+    def forward(self):
+        net, B, T, H = self.net, self.B, self.T, self.net.H
+        st = _lib.stream_ptr()
+        x = self.feats.view(B * T, -1)
+        for l in range(net.L):
+            ops.gemm(x, net.cat_view("weight_ih", l), transB=True, bias=net.cat_view("bias_ih", l), out=self.G,
+                     precision=self.precision)
+            _lib.call("dl4ss_birnn_fwd", LSTM, ops.PREC[self.precision], B, T, H, _lib.ptr(self.G),
+                      _lib.ptr(net.cat_view("weight_hh", l)), _lib.ptr(net.cat_view("bias_hh", l)),
+                      _lib.ptr(self.out[l]), _lib.ptr(self.hprev[l]), _lib.ptr(self.act[l]), _lib.ptr(self.cs[l]),
+                      _lib.ptr(self.rnn_ws), self.ws_bytes, _lib.ptr(self.status), st)
+            x = self.out[l].view(B * T, 2 * H)
+        _lib.call("dl4ss_time_mean", _lib.ptr(self.out[-1]), B, T, 2 * H, _lib.ptr(self.mean), st)
+        _lib.call("dl4ss_cls_head_fwd", _lib.ptr(self.mean), _lib.ptr(net.view("Linear.weight")),
+                  _lib.ptr(net.view("Linear.bias")), B, 2 * H, net.num_labels, _lib.ptr(self.logits),
+                  _lib.ptr(self.prob), st)
+        return self.prob
+
+    # ------------------------------------------------------------------ loss + head backward
+    def loss_and_grad(self, y_map=None):
+        """y_map (B, N_lab): the multi-hot of ``multi_label_vector``.  Writes the loss, the Linear's
+        gradients and the top layer's ``dOut_bcast``; returns the loss tensor (not synced)."""
+        net = self.net
+        if y_map is not None:
+            self.y.copy_(y_map)
+        g = net.grad
+        _lib.call("dl4ss_cls_head_loss_bwd", _lib.ptr(self.prob), _lib.ptr(self.y), _lib.ptr(self.mean),
+                  _lib.ptr(net.view("Linear.weight")), self.B, 2 * net.H, net.num_labels, self.T, _lib.ptr(self.loss),
+                  _lib.ptr(self.dz), _lib.ptr(net.view("Linear.weight", g)), _lib.ptr(net.view("Linear.bias", g)),
+                  _lib.ptr(self.dmb), _lib.stream_ptr())
+        return self.loss
+
+    # ------------------------------------------------------------------ backward
+    def backward(self):
+        net, B, T, H = self.net, self.B, self.T, self.net.H
+        BT, NGH = B * T, 4 * H
+        g = net.grad
+        st = _lib.stream_ptr()
+        dH = self._zero_dout
+        for l in range(net.L - 1, -1, -1):
+            top = l == net.L - 1
+            dG = self.G
+            _lib.call("dl4ss_birnn_bwd_ex", LSTM, ops.PREC[self.precision], B, T, H, _lib.ptr(dH),
+                      _lib.ptr(self.dmb) if top else None, _lib.ptr(net.cat_view("weight_hh", l)),
+                      _lib.ptr(self.act[l]), _lib.ptr(self.cs[l]), _lib.ptr(self.hprev[l]), _lib.ptr(dG), None, None,
+                      None, None, None, _lib.ptr(self.rnn_ws), self.ws_bytes, _lib.ptr(self.status), st)
+            xl = self.feats.view(BT, -1) if l == 0 else self.out[l - 1].view(BT, 2 * H)
+            # unsplit (splitk = 1): no float atomics, the step repeats bit for bit
+            ops.gemm(dG, xl, transA=True, out=net.cat_view("weight_ih", l, g), precision=self.precision)
+            db = net.cat_view("bias_ih", l, g)
+            db.zero_()
+            ops.colsum(dG, db)
+            net.cat_view("bias_hh", l, g).copy_(db)  # LSTM: dGh == dG
+            whh_g = net.cat_view("weight_hh", l, g)
+            hp = self.hprev[l].view(BT, 2 * H)
+            for d in range(2):
+                ops.gemm(dG[:, d * NGH:(d + 1) * NGH], hp[:, d * H:(d + 1) * H], transA=True,
+                         out=whh_g[d * NGH:(d + 1) * NGH], precision=self.precision)
+            if l > 0:
+                dH = self.dH[l % 2] if len(self.dH) > 1 else self.dH[0]
+                ops.gemm(dG, net.cat_view("weight_ih", l), out=dH, precision=self.precision)
+
+    # ------------------------------------------------------------------ Adam
+    def optimizer_step(self):
+        """Adam on the flat buffers; refused on device (parameters untouched, loss[0] = NaN, status[1]
+        counts it) when a recurrence hand-off of this step timed out."""
+        self.step_count += 1
+        ops.adam_(self.net.flat, self.net.grad, self.m, self.v, self.step_count, self.lr, self.betas, self.eps,
+                  status=self.status, loss=self.loss)
+
+    def step(self, raw=None, gains=None, y_map=None, feats=None):
+        """One training step on device-resident inputs; returns the loss tensor (not synced)."""
+        self.features(raw, gains, feats)
+        self.forward()
+        loss = self.loss_and_grad(y_map)
+        self.backward()
+        self.optimizer_step()
+        return loss
+
+    def check(self):
+        """Raise if a recurrence hand-off timed out since the last check (the guarded Adam already
+        refused every update from then on); the refused steps leave step_count, the status word and the
+        hand-off workspace are reset, so training can continue."""
+        torch.cuda.synchronize()
+        s, refused = (int(x) for x in self.status.tolist())
+        if s or refused:
+            self.status.zero_()
+            self.rnn_ws.zero_()
+            self.step_count -= refused
+            raise RuntimeError(f"BiRNN hand-off timed out (status {s}): {refused} update(s) refused")

@@ -50,4 +50,17 @@ def install(shims=True, drivers=False):
         sys.path.insert(1, DRIVERS)
     if shims and SHIMS not in sys.path:
         sys.path.append(SHIMS)
+    _export_count_multi_acc()
     return PATH
+
+
+def _export_count_multi_acc():
+    """``from test_multi_labels_speech import count_multi_acc`` is the reference's surface
+    (Torch_multi/test_multi_labels_speech.py:300-351); the restatement lives in ``multi_labels_acc``, so
+    the mirror of that module (numpy only, cheap to import) gets the name here, under both of its
+    import names."""
+    import importlib
+
+    acc = importlib.import_module("dl4ss_amd.compat.multi_labels_acc").count_multi_acc
+    for name in ("test_multi_labels_speech", "dl4ss_amd.compat.test_multi_labels_speech"):
+        importlib.import_module(name).count_multi_acc = acc

@@ -50,8 +50,8 @@ constexpr int WMAX = 64;     // fwd weights per thread (generic path)
 constexpr int RPLMAX = 20;   // bwd rows per thread
 constexpr int KGLMAX = 6;    // bwd k per thread
 constexpr int HMAX = 320;    // largest hidden size of the training kernels (sizes per-thread offset arrays)
-constexpr int HMAX_L = 640;  // largest hidden size of the forward-only (inference) instantiations: the
-                             // H = 600 speaker classifier of EvalVer.py:305-326 / GRID.py:178-199
+constexpr int HMAX_L = 640;  // largest hidden size of the generic kernels' large-H instantiations (forward and
+                             // BPTT): the H = 600 speaker classifier of EvalVer.py:305-326 / GRID.py:178-199
 constexpr int DL4SS_RNN_WS_ZEROED = 0x100;  // precision flag: workspace already zero (no memset)
 constexpr int DL4SS_RNN_DEFER_BIAS = 0x400;  // BPTT: leave the per-row bias partials for dl4ss_birnn_bias_reduce
 constexpr int DL4SS_RNN_DGH_PAD8 = 0x200;  // precision flag (bwd): dGh_bf16 direction stride padded to 8
@@ -1522,12 +1522,15 @@ __global__ __launch_bounds__(NT, 1) void rnn_fwd_pk_kernel(RnnArgs a) {
 // A fragments (output unit k on the MFMA row, gate row r on its K), dgh is staged
 // in LDS as the bf16 B image [batch][r]; each 16-unit tile's D lanes publish their
 // granules directly -- no partial-sum buffer, no third barrier.
-template <int CELL, int BC, int RPL_T, int KGL_T, bool MF>
+// HM: the largest hidden size of the instantiation (sizes the per-thread offset arrays, the MFMA unit
+// tiles per wave and the MFMA path's transpose area): HMAX for the mask nets, HMAX_L for the H = 600
+// speaker classifier (test_multi_labels_speech.py:240-246,444).
+template <int CELL, int BC, int RPL_T, int KGL_T, bool MF, int HM = HMAX>
 __global__ __launch_bounds__(NT, 1) void rnn_bwd_kernel(RnnArgs a) {
   constexpr int NGATE = CELL == CELL_LSTM ? 4 : 3;
   constexpr int RPLN = MF ? 1 : (RPL_T > 0 ? RPL_T : RPLMAX);  // rows per thread (compile-time)
   constexpr int KGLN = MF ? 1 : (KGL_T > 0 ? KGL_T : KGLMAX);  // k per thread (compile-time)
-  constexpr int MTWMAX = (HMAX / 16 + 3) / 4;                    // MFMA unit tiles per wave
+  constexpr int MTWMAX = (HM / 16 + 3) / 4;                      // MFMA unit tiles per wave
   constexpr int KSRMAX = (4 * 20 + 31) / 32;                     // MFMA K-steps over gate rows
   const int H = a.H, T = a.T, J = a.J, NG = a.NG;
   const int R = NGATE * J;
@@ -1591,7 +1594,7 @@ __global__ __launch_bounds__(NT, 1) void rnn_bwd_kernel(RnnArgs a) {
     }
   }
   // gather role: offsets of the NG partials of every own (b, unit), fixed per launch
-  constexpr int GM = (BC * (HMAX + 20) + NROLE - 1) / NROLE;
+  constexpr int GM = (BC * (HM + 20) + NROLE - 1) / NROLE;
   int goff[GM];
 #pragma unroll
   for (int g = 0; g < GM; ++g) {
@@ -1603,7 +1606,7 @@ __global__ __launch_bounds__(NT, 1) void rnn_bwd_kernel(RnnArgs a) {
     }
   }
   // publish role: (b, k) of every granule this thread writes, fixed per launch
-  constexpr int GP = (BC * HMAX + NROLE - 1) / NROLE;
+  constexpr int GP = (BC * HM + NROLE - 1) / NROLE;
   int psrc[GP];
 #pragma unroll
   for (int g = 0; g < GP; ++g) {
@@ -1637,8 +1640,8 @@ __global__ __launch_bounds__(NT, 1) void rnn_bwd_kernel(RnnArgs a) {
     const float* p = nullptr;
     int stride = 2 * H, shift = 0;
     if (valid) {
-      if (slot == 0) {
-        p = a.dOut + (long long)ib * T * 2 * H + d * H + ij;
+      if (slot == 0) {  // dOut NULL (a top layer fed by dOut_bcast alone): the item stays null and reads as zero
+        if (a.dOut) p = a.dOut + (long long)ib * T * 2 * H + d * H + ij;
       } else if (slot <= 4) {
         p = a.act + ((long long)ib * T * 2 + d) * AH + (slot - 1) * H + ij;
         stride = 2 * AH;
@@ -2575,8 +2578,14 @@ __global__ __launch_bounds__(NT, 1) void rnn_bwd_pk_kernel(RnnArgs a) {
 
 // compile-time (rows, k) per thread of the BPTT matvec: the shipped H = 300 plans
 // (LSTM R=80: 20 x 3, GRU R=60: 20 x 2) and the generic (guard-free, zero-padded) maxima
-void bwd_dims(int rpl, int kgl, int& rpln, int& kgln) {
-  if ((rpl == 20 && kgl == 3) || (rpl == 20 && kgl == 2)) {
+// big (H > HMAX): the fp32 plan of the H = 600 LSTM (J = 12: 48 gate rows over 3 parts of 16, 170
+// k-groups of 4) and every other wide plan within 16 x 4 run one 16 x 4 instantiation; the rest (the
+// H = 600 GRU: J = 17, parts of 17 rows) the runtime-bounds one
+void bwd_dims(int rpl, int kgl, int& rpln, int& kgln, bool big = false) {
+  if (big && rpl <= 16 && kgl <= 4) {
+    rpln = 16;
+    kgln = 4;
+  } else if (!big && ((rpl == 20 && kgl == 3) || (rpl == 20 && kgl == 2))) {
     rpln = rpl;
     kgln = kgl;
   } else {
@@ -2630,12 +2639,12 @@ struct Plan {
   bool fwd_pk;                       // packed hand-off forward (rnn_fwd_pk_kernel) applies
   size_t smem_fwd_pk;
   bool bwd_pk;                       // packed hand-off BPTT (rnn_bwd_pk_kernel) applies
-  bool big;                          // H > HMAX: forward-only instantiations (HM = HMAX_L)
+  bool big;                          // H > HMAX: the generic kernels' large-H instantiations (HM = HMAX_L)
   size_t smem_bwd_pk;
 };
 
 // mf: plan for the bf16 MFMA matvec (the fp32 VALU forward's per-thread weight limit
-// KPL <= WMAX does not apply).  H > HMAX is the forward-only large-H plan (HM = HMAX_L).
+// KPL <= WMAX does not apply).  H > HMAX is the large-H plan (HM = HMAX_L): generic kernels only.
 // Co-residency budget of one persistent launch (both directions, all batch chunks): every
 // workgroup must be resident at once, so the plan keeps 2 * nchunk * NG within the device's
 // CU count minus 1/16 of it (240 of 256 on a full MI355X; 30 on a 32-CU CPX partition),
@@ -2688,12 +2697,12 @@ bool make_plan(int cell, int B, int H, Plan& p, bool mf = true, int max_wg = 0) 
     p.KP = KP; p.KPL = KPL; p.HP = KP * KPL;
     p.RP = best_rp; p.RPL = (R + best_rp - 1) / best_rp; p.KG = best_kg; p.KGL = (H + best_kg - 1) / best_kg;
     int rpln, kgln;
-    bwd_dims(p.RPL, p.KGL, rpln, kgln);
+    bwd_dims(p.RPL, p.KGL, rpln, kgln, p.big);
     p.smem_fwd = sizeof(float) * (BC * p.HP + KP * BC * R + 2 * BC * J * 4);
     p.smem_bwd = sizeof(float) * (BC * p.RP * rpln + NG * BC * J + 3 + p.RP * BC * p.KG * kgln + 2 * BC * J * 8);
     const int SHB = (p.big ? HMAX_L : HMAX) + 8, MT = (R + 15) / 16, SDG = (4 * 20 + 31) / 32 * 32 + 8;
     p.smem_fwd_mf = 2 * 16 * SHB + sizeof(float) * (BC * MT * 16 + 2 * BC * J * 4);
-    p.smem_bwd_mf = 2 * 16 * SDG + sizeof(float) * (NG * BC * J + 3 + BC * HMAX + 2 * BC * J * 8);
+    p.smem_bwd_mf = 2 * 16 * SDG + sizeof(float) * (NG * BC * J + 3 + BC * (p.big ? HMAX_L : HMAX) + 2 * BC * J * 8);
     p.fwd_pk = !p.big && J % 2 == 0 && H % 2 == 0 && J <= PKU && NG <= 16 && (R + 15) / 16 <= (FWD_NPW == 3 ? 5 : FWD_NPW == 2 ? 6 : 7);
     p.bwd_pk = !p.big && J % 4 == 0 && H % 4 == 0 && NG <= 16;
     p.smem_bwd_pk = 2 * 16 * SDG + sizeof(float) * (((16 * BC * J + 3) & ~3) + 4 * BC * ((HMAX / 16 + 3) / 4 * 16 + 4) +
@@ -2754,9 +2763,16 @@ int launch_fwd(const RnnArgs& a, bool mf, bool pk, int grid, size_t smem, hipStr
 template <int CELL, int BC>
 int launch_bwd(const RnnArgs& a, bool mf, bool pk, int grid, size_t smem, hipStream_t st) {
   int rpln, kgln;
-  bwd_dims(a.RPL, a.KGL, rpln, kgln);
+  bwd_dims(a.RPL, a.KGL, rpln, kgln, a.H > HMAX);
 #ifdef RNN_EXP_MINIMAL
   if (BC != 4 || !mf || !pk) return (int)hipErrorNotSupported;
+#else
+  if (a.H > HMAX) {  // large-H instantiations of the generic kernel (the H = 600 classifier); never packed
+    if (pk) return (int)hipErrorInvalidValue;
+    if (mf) return launch_resident(rnn_bwd_kernel<CELL, BC, 0, 0, true, HMAX_L>, grid, smem, st, a);
+    if (rpln == 16 && kgln == 4) return launch_resident(rnn_bwd_kernel<CELL, BC, 16, 4, false, HMAX_L>, grid, smem, st, a);
+    return launch_resident(rnn_bwd_kernel<CELL, BC, 0, 0, false, HMAX_L>, grid, smem, st, a);
+  }
 #endif
   if constexpr (BC == 4) {  // the dH GEMM's split-K slabs summed by the top layer (DL4SS_RNN_DOUT_SLABS)
     if (mf && pk && a.dout_ns == 2) return launch_resident(rnn_bwd_pk_kernel<CELL, 4, 2>, grid, smem, st, a);
@@ -2877,8 +2893,8 @@ static long long handoff_bytes(const Plan& p, int H) {
   long long fwd = groups * 2 * p.BC * H * 8;
   const long long fwd_pk = groups * 4 * p.BC * p.NG * 8 * 8;
   if (fwd_pk > fwd) fwd = fwd_pk;
-  if (p.big) return fwd;  // forward only
   long long bwd = groups * 2 * p.NG * p.BC * H * 8;
+  if (p.big) return ((fwd > bwd ? fwd : bwd) + 255) / 256 * 256;  // generic kernels only: no packed forms, no counters
   const long long bwd_pk = groups * 4LL * p.NG * p.BC * (((H + 1) / 2 + 1) & ~1) * 8;
   if (bwd_pk > bwd) bwd = bwd_pk;
   const long long n = fwd > bwd ? fwd : bwd;
@@ -3115,6 +3131,7 @@ DL4SS_API int dl4ss_birnn_bwd(int cell, int precision, int B, int T, int H, cons
                               const float* W_hh, const float* act, const float* cs, const float* hprev, float* dG,
                               float* dGh, void* workspace, long long ws_bytes, int* status, void* stream) {
   DL4SS_REQUIRE(dG && (cell == CELL_LSTM || dGh));
+  DL4SS_REQUIRE(H <= HMAX && dOut);  // the mask nets' entry point; H <= HMAX_L: dl4ss_birnn_bwd_ex
   return dl4ss_birnn_bwd_ex(cell, precision, B, T, H, dOut, dOut_bcast, W_hh, act, cs, hprev, dG, dGh, nullptr,
                             nullptr, nullptr, nullptr, workspace, ws_bytes, status, stream);
 }
@@ -3131,11 +3148,32 @@ DL4SS_API int dl4ss_birnn_bwd_ex(int cell, int precision, int B, int T, int H, c
   const int dout_ns = ((precision & DL4SS_RNN_DOUT_SLABS_MASK) >> 12) + 1;
   precision &= ~(DL4SS_RNN_WS_ZEROED | DL4SS_RNN_DGH_PAD8 | DL4SS_RNN_DEFER_BIAS | DL4SS_RNN_DOUT_SLABS_MASK);
   DL4SS_REQUIRE(precision == 0 || precision == 1);
-  DL4SS_REQUIRE(B > 0 && T > 0 && H > 0 && dOut && W_hh && act && workspace && status);
+  DL4SS_REQUIRE(B > 0 && T > 0 && H > 0 && H <= HMAX_L && W_hh && act && workspace && status);
+  // the classifier's top layer: its only gradient is d(mean_t h), so dOut may be NULL (read as zero) when
+  // dOut_bcast is given -- in the generic kernel (every H > HMAX plan), checked below
+  DL4SS_REQUIRE(dOut || dOut_bcast);
   DL4SS_REQUIRE(dG || dG_bf16);
   DL4SS_REQUIRE(cell == CELL_GRU ? ((dGh || dGh_bf16) && hprev) : (cs != nullptr));
-  DL4SS_REQUIRE(H <= HMAX);  // BPTT is built for the mask nets (H <= 320); the large-H plan is forward only
   Plan p;
+  if (precision == 0 && H > HMAX && !make_plan(cell, B, H, p, false)) {
+    // the wide layer's fp32 plan does not fit at this batch: consecutive sub-batch launches of the
+    // forward's sub-batch size (split_batch; rows never interact), each zeroing the shared hand-off
+    // workspace itself (stream order keeps them apart)
+    const int bs = split_batch(cell, B, H, false, p);
+    DL4SS_REQUIRE(bs > 0 && dout_ns == 1 && dG && !dG_bf16 && !dGh_bf16 && !db_ih && !db_hh && (cell == CELL_LSTM || dGh));
+    const long long GH = (cell == CELL_LSTM ? 4LL : 3LL) * H;
+    for (int b0 = 0; b0 < B; b0 += bs) {
+      const long long r = (long long)b0 * T;  // (b, t) rows before the sub-batch
+      const int rc = dl4ss_birnn_bwd_ex(cell, 0, B - b0 < bs ? B - b0 : bs, T, H, dOut ? dOut + r * 2 * H : nullptr,
+                                        dOut_bcast ? dOut_bcast + (long long)b0 * 2 * H : nullptr, W_hh,
+                                        act + r * 2 * 4 * H, cs ? cs + r * 2 * H : nullptr,
+                                        hprev ? hprev + r * 2 * H : nullptr, dG + r * 2 * GH,
+                                        dGh ? dGh + r * 2 * GH : nullptr, nullptr, nullptr, nullptr, nullptr, workspace,
+                                        ws_bytes, status, stream);
+      if (rc) return rc;
+    }
+    return 0;
+  }
   DL4SS_REQUIRE(make_plan(cell, B, H, p, precision == 1));
   DL4SS_REQUIRE(ws_bytes >= workspace_bytes(p, H));
   hipStream_t st = as_stream(stream);
@@ -3143,6 +3181,12 @@ DL4SS_API int dl4ss_birnn_bwd_ex(int cell, int precision, int B, int T, int H, c
   const bool mf = precision == 1;
   // the packed BPTT at BC >= 4 reads the cell-major act that only the packed forward writes
   const bool pk = mf && p.bwd_pk && T < 65535 && (p.BC < 4 || act_cell_major(p));
+  // every refusal comes before the first device call (the workspace fill below)
+  DL4SS_REQUIRE(dOut || !pk);  // the packed kernel's step loader reads dOut unconditionally
+  // bf16 gradient copies, dropping the fp32 ones and the fused bias sums need the packed kernel
+  DL4SS_REQUIRE(pk || (!dG_bf16 && !dGh_bf16 && !db_ih && !db_hh && dG && (cell == CELL_LSTM || dGh)));
+  // split-K dOut slabs: the packed BPTT's step-factor prefetch at batch chunks of 4 sums them
+  DL4SS_REQUIRE(dout_ns == 1 || (pk && p.BC == 4));
   const long long HG = ((H + 1) / 2 + 1) & ~1;
   if (!prezeroed) {
     hipError_t e =
@@ -3150,10 +3194,6 @@ DL4SS_API int dl4ss_birnn_bwd_ex(int cell, int precision, int B, int T, int H, c
     if (e == hipSuccess && pk) e = hipMemsetAsync(static_cast<char*>(workspace) + ctl_offset(p, H), 0, 256, st);
     if (e != hipSuccess) return (int)e;
   }
-  // bf16 gradient copies, dropping the fp32 ones and the fused bias sums need the packed kernel
-  DL4SS_REQUIRE(pk || (!dG_bf16 && !dGh_bf16 && !db_ih && !db_hh && dG && (cell == CELL_LSTM || dGh)));
-  // split-K dOut slabs: the packed BPTT's step-factor prefetch at batch chunks of 4 sums them
-  DL4SS_REQUIRE(dout_ns == 1 || (pk && p.BC == 4));
   RnnArgs a{};
   fill_args(a, p, B, T, H);
   a.Whh = W_hh; a.act = const_cast<float*>(act); a.cs = const_cast<float*>(cs);

@@ -148,19 +148,35 @@ class ClassifierNet:
             off += (math.prod(shape) + 3) // 4 * 4  # 16-B aligned views
         self.device = torch.device(device)
         self.flat = torch.zeros(off, device=self.device, dtype=torch.float32)
+        self.grad = None  # the flat gradient, same layout: allocated by a ClassifierTrainer on this net
         self.reset_parameters(seed)
 
-    def view(self, name):
+    def view(self, name, buf=None):
+        """The parameter ``name``, or its counterpart in ``buf`` (a flat buffer of the same layout:
+        the gradient, an Adam moment)."""
         off, shape = self.offsets[name]
-        return self.flat[off:off + math.prod(shape)].view(shape)
+        return (self.flat if buf is None else buf)[off:off + math.prod(shape)].view(shape)
 
-    def cat_view(self, kind, l):
+    def cat_view(self, kind, l, buf=None):
         """[fwd; reverse] of layer l (adjacent in the flat buffer by construction)."""
         a = self.view(f"layer.{kind}_l{l}")
         off = self.offsets[f"layer.{kind}_l{l}"][0]
         n = a.numel()
-        v = self.flat[off:off + 2 * n]
+        v = (self.flat if buf is None else buf)[off:off + 2 * n]
         return v.view(2 * a.shape[0], *a.shape[1:]) if a.dim() == 2 else v
+
+    def named_parameters(self):
+        """(name, tensor) pairs as torch's ``named_parameters()`` yields them, under the reference's names, in
+        the flat buffer's order (each layer's forward / reverse tensors adjacent)."""
+        for name, _ in self.specs:
+            yield name, self.view(name)
+
+    def grad_view(self, name):
+        """The gradient of ``name`` in the flat gradient a ClassifierTrainer keeps on this net
+        (``self.grad``: None until a trainer is built)."""
+        if self.grad is None:
+            raise RuntimeError("no gradient buffer: build a ClassifierTrainer on this net first")
+        return self.view(name, self.grad)
 
     def reset_parameters(self, seed=1):
         """torch defaults: nn.LSTM U(+-1/sqrt(H)), nn.Linear U(+-1/sqrt(fan_in))."""

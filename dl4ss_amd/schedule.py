@@ -6,6 +6,8 @@
 * ``Torch_multi/main_run_multi_selfSS_dB.py:441-444``: halved every 50 epochs, no floor.
 * ``main_run_sstune_cRM_EvalVer.py:627-631`` has the 50-epoch / ``>= 5e-6`` form switched
   off (``if 0 and ...``): a constant lr.
+* ``Torch_multi/test_multi_labels_speech.py:405-407`` (the speaker classifier): halved every 50
+  epochs from epoch 0 on, no floor.
 
 ``SepTrainer.lr`` is read by every Adam launch, so applying a schedule is assigning it.
 """
@@ -34,6 +36,12 @@ def evalver(lr=2e-4):
 
 def selfss_db(lr=2e-4):
     """selfSS_dB.py:442-444."""
+    return LRHalving(lr, every=50, floor=None)
+
+
+def classifier(lr=1e-5):
+    """Torch_multi/test_multi_labels_speech.py:405-407: halved at every epoch_idx % 50 == 0, epoch 0
+    included, no floor -- the optimizer is built with 1e-5 (:395), so epochs 0-49 run at 5e-6."""
     return LRHalving(lr, every=50, floor=None)
 
 

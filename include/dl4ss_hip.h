@@ -268,7 +268,8 @@ int dl4ss_birnn_fwd_xw_ex(int cell, int B, int T, int H, const void* x_bf16, int
 int dl4ss_birnn_fwd_xw_supported(int cell, int B, int T, int H, int Kin);
 /* BPTT of one layer: dOut (B,T,2H) (+ dOut_bcast (B,2H) at every t, may be NULL) ->
  * dG (B,T,2,NG*H) grad of the input projection (pre-activation) and, for GRU, dGh
- * grad of W_hh h + b_hh (for LSTM they coincide; dGh may be NULL). */
+ * grad of W_hh h + b_hh (for LSTM they coincide; dGh may be NULL).  The mask nets' entry point:
+ * H <= 320 (a wider layer is refused here; dl4ss_birnn_bwd_ex runs it). */
 int dl4ss_birnn_bwd(int cell, int precision, int B, int T, int H, const float* dOut, const float* dOut_bcast,
                     const float* W_hh, const float* act, const float* cs, const float* hprev, float* dG, float* dGh, void* workspace,
                     long long ws_bytes, int* status, void* stream);
@@ -276,7 +277,15 @@ int dl4ss_birnn_bwd(int cell, int precision, int B, int T, int H, const float* d
 /* dl4ss_birnn_bwd with bf16 extras (precision 1, packed-hand-off kernel only): dG_bf16 /
  * dGh_bf16 (B,T,2,NG*H) receive bf16 copies (the weight-gradient / dX GEMM operands),
  * dG / dGh may then be NULL, and db_ih / db_hh (2, NG*H) are ACCUMULATED with the sums
- * over (b,t) of dG / dGh (the bias gradients; fp32 atomics, one per cell and gate). */
+ * over (b,t) of dG / dGh (the bias gradients; fp32 atomics, one per cell and gate).
+ * Large hidden sizes (320 < H <= 640; H > 640 is refused before any device call): the BPTT of the
+ * H = 600 speaker classifier, loss.backward() through nn.LSTM(129, 600, 3, bidirectional) at
+ * Torch_multi/test_multi_labels_speech.py:444 (:240-246).  Generic kernel only (precision 0 or 1, both
+ * cells, gate-major act as the large-H forward writes it): no bf16 copies, no fused bias sums, no dOut
+ * slabs, fp32 dG (and dGh for GRU) required.  Wherever the generic kernel runs (every H > 320 plan,
+ * precision 0, bf16 plans without the packed form) dOut may be NULL (read as zero) when dOut_bcast is
+ * given: the classifier's top layer, whose only gradient is d(mean_t h).  A precision-0 plan that does not fit
+ * the co-residency budget at B runs as the forward's sub-batch launches (see dl4ss_birnn_fwd). */
 int dl4ss_birnn_bwd_ex(int cell, int precision, int B, int T, int H, const float* dOut, const float* dOut_bcast,
                        const float* W_hh, const float* act, const float* cs, const float* hprev, float* dG,
                        float* dGh, void* dG_bf16, void* dGh_bf16, float* db_ih, float* db_hh, void* workspace,
@@ -453,6 +462,21 @@ int dl4ss_mask_split(const float* mask, const float* x, long long n, float* pred
 /* mean over t of h (B,T,D) -> (B,D): the classifier's torch.mean(x, 1) (GRID.py:196,
  * EvalVer.py:323) and ADDJUST's time mean (EvalVer.py:373). */
 int dl4ss_time_mean(const float* h, int B, int T, int D, float* mean_out, void* stream);
+/* Classifier head forward: m (B, D) the time mean of the top BiLSTM layer (D = 2H), W (C, D), b (C)
+ * -> logits z (B, C) and p = sigmoid(z): self.Linear + F.sigmoid of MIX_SPEECH_classifier
+ * (Torch_multi/test_multi_labels_speech.py:259-263).  No allocation; B <= 65535. */
+int dl4ss_cls_head_fwd(const float* m, const float* W, const float* b, int B, int D, int C, float* z, float* p,
+                       void* stream);
+/* Classifier loss and head backward of one training step (test_multi_labels_speech.py:397,437,444):
+ * nn.MultiLabelSoftMarginLoss applied, as the reference does, to the sigmoid output p (not the logits)
+ * against the multi-hot y (B, C), and its gradient through sigmoid, Linear and the time mean over T:
+ *   loss (1) = -1/(B C) sum [ y log sigmoid(p) + (1 - y) log sigmoid(-p) ]
+ *   dz (B, C) = (sigmoid(p) - y) / (B C) * p (1 - p),  dW (C, D) = dz^T m,  db (C) = sum_b dz,
+ *   dOut_bcast (B, D) = dz W / T  -- the constant-over-t dOut term of the top layer's BPTT
+ *   (dl4ss_birnn_bwd_ex with dOut NULL).
+ * All outputs are written; fixed-order sums, no atomics (repeatable bit for bit); no allocation. */
+int dl4ss_cls_head_loss_bwd(const float* p, const float* y, const float* m, const float* W, int B, int D, int C,
+                            int T, float* loss, float* dz, float* dW, float* db, float* dOut_bcast, void* stream);
 
 /* ---- BSS-eval (replaces the un-vendored separation.bss_eval_sources of
  *      Torch_multi/bss_test.py:5,55 -- BSS_EVAL v3, 512-tap distortion filters) ---- */
