@@ -93,13 +93,22 @@ SIGNATURES = {
     "dl4ss_attn_align_finalize": [P, LL, I, I, I, I, P, P, P, P, P, P, P],
     "dl4ss_cls_head_fwd": [P, P, P, I, I, I, P, P, P],
     "dl4ss_cls_head_loss_bwd": [P, P, P, P, I, I, I, I, P, P, P, P, P, P],
+    "dl4ss_disc_dims": [I, I, P],
+    "dl4ss_disc_ws_bytes": [I, I, I],
+    "dl4ss_disc_conv1_fwd": [I, P, P, P, I, I, I, P, P],
+    "dl4ss_disc_conv64_fwd": [I, P, P, P, I, I, I, P, P],
+    "dl4ss_disc_head_fwd": [I, P, P, P, I, I, I, P, P, P],
+    "dl4ss_disc_head_bwd": [I, P, P, P, P, F, I, I, I, P, P, P, P, P, P],
+    "dl4ss_disc_conv64_bwd": [I, P, P, P, P, I, I, I, P, P, P, P, LL, P],
+    "dl4ss_disc_conv1_bwd": [I, P, P, P, P, I, I, I, P, P, P, P, LL, P],
 }
 # entry points that return a value rather than a hipError_t
 RESTYPES = {"dl4ss_birnn_workspace_bytes": ctypes.c_longlong, "dl4ss_colsum_bf16_part_bytes": ctypes.c_longlong,
             "dl4ss_gemm_bf16_gl_ws_bytes": ctypes.c_longlong,
             "dl4ss_gemm_bf16_gl_grouped_ws_bytes": ctypes.c_longlong, "dl4ss_attn_nblk": ctypes.c_int,
             "dl4ss_attn_dot_nblk": ctypes.c_int, "dl4ss_attn_align_nblk": ctypes.c_int,
-            "dl4ss_attn_align_part_floats": ctypes.c_longlong, "dl4ss_debug_set_spin_limit": None,
+            "dl4ss_attn_align_part_floats": ctypes.c_longlong, "dl4ss_disc_ws_bytes": ctypes.c_longlong,
+            "dl4ss_debug_set_spin_limit": None,
             "dl4ss_debug_set_place_force": None, "dl4ss_debug_set_rnn_max_wg": None}
 
 _lib = None

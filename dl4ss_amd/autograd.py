@@ -321,3 +321,96 @@ def top_k_mask_device(prob, alpha, top_k):
     _lib.call("dl4ss_top_k_mask", _lib.ptr(prob), B, N, float(alpha), int(top_k), _lib.ptr(mask), _lib.ptr(idx),
               _lib.ptr(cnt), _lib.stream_ptr())
     return mask, idx[:, :top_k], cnt
+
+
+# --------------------------------------------------------------------------- Discriminator
+def disc_dims(T, F):
+    """(features, [H1, W1, H2, W2, H3, W3]) of a (T, F) map through the three stride-2 3x3 'valid' convs
+    (host only); raises for a map smaller than 15 x 15."""
+    hw = (ctypes.c_int * 6)()
+    feat = _lib.query("dl4ss_disc_dims", int(T), int(F), hw)
+    if feat < 0:
+        raise RuntimeError(f"Discriminator: a ({T}, {F}) map is smaller than the 15 x 15 minimum")
+    return feat, list(hw)
+
+
+def _disc_act_dtype(precision):
+    return torch.bfloat16 if ops.PREC[precision] == 1 else torch.float32
+
+
+def disc_fwd_impl(spec, w1, b1, w2, b2, w3, b3, wf, bf, precision):
+    """spec (N, T, F) -> (score (N, 1), y1, y2, y3): the saved post-ReLU activations are channels-last
+    (N, H, W, 64), fp32 or (precision 'bf16') bfloat16.  Shared by DiscriminatorFn and dl4ss::discriminator."""
+    spec = _c(spec.float())
+    N, T, F = spec.shape
+    feat, hw = disc_dims(T, F)
+    if wf.numel() != feat:
+        raise RuntimeError(f"Discriminator: final.weight has {wf.numel()} features, a ({T}, {F}) map gives {feat}")
+    prec, dt, dev, st = ops.PREC[precision], _disc_act_dtype(precision), spec.device, _lib.stream_ptr()
+    y1, y2, y3 = (torch.empty(N, hw[2 * l], hw[2 * l + 1], 64, dtype=dt, device=dev) for l in range(3))
+    _lib.call("dl4ss_disc_conv1_fwd", prec, _lib.ptr(spec), _lib.ptr(_c(w1)), _lib.ptr(_c(b1)), N, T, F, _lib.ptr(y1),
+              st)
+    _lib.call("dl4ss_disc_conv64_fwd", prec, _lib.ptr(y1), _lib.ptr(_c(w2)), _lib.ptr(_c(b2)), N, hw[0], hw[1],
+              _lib.ptr(y2), st)
+    _lib.call("dl4ss_disc_conv64_fwd", prec, _lib.ptr(y2), _lib.ptr(_c(w3)), _lib.ptr(_c(b3)), N, hw[2], hw[3],
+              _lib.ptr(y3), st)
+    z = torch.empty(N, device=dev)
+    score = torch.empty(N, 1, device=dev)
+    _lib.call("dl4ss_disc_head_fwd", prec, _lib.ptr(y3), _lib.ptr(_c(wf)), _lib.ptr(_c(bf)), N, hw[4], hw[5],
+              _lib.ptr(z), _lib.ptr(score), st)
+    return score, y1, y2, y3
+
+
+def disc_bwd_impl(dscore, spec, w1, w2, w3, wf, score, y1, y2, y3, precision, need_dx=True, target=None):
+    """(dspec or None, dw1, db1, dw2, db2, dw3, db3, dwf, dbf) from dscore (N, 1).  With ``dscore`` None the
+    head fuses the loss mean_n (score_n - target)^2 (target 1 or 0) and its scalar is appended to the result."""
+    spec = _c(spec.float())
+    N, T, F = spec.shape
+    _, hw = disc_dims(T, F)
+    prec, dev, st = ops.PREC[precision], spec.device, _lib.stream_ptr()
+    w1, w2, w3, wf = _c(w1), _c(w2), _c(w3), _c(wf)
+    wsn = _lib.query("dl4ss_disc_ws_bytes", N, T, F)
+    if wsn < 0:
+        raise RuntimeError(f"Discriminator shape unsupported (N={N}, T={T}, F={F})")
+    ws = torch.empty((wsn + 3) // 4, device=dev)
+    dz = torch.empty(N, device=dev)
+    dwf, dbf = torch.empty_like(wf), torch.empty(1, device=dev)
+    dw1, dw2, dw3 = torch.empty_like(w1), torch.empty_like(w2), torch.empty_like(w3)
+    db1, db2, db3 = (torch.empty(64, device=dev) for _ in range(3))
+    dy3, dy2, dy1 = torch.empty_like(y3), torch.empty_like(y2), torch.empty_like(y1)
+    loss = torch.empty(1, device=dev) if dscore is None else None
+    ds = _c(dscore.float()) if dscore is not None else None
+    _lib.call("dl4ss_disc_head_bwd", prec, _lib.ptr(y3), _lib.ptr(wf), _lib.ptr(_c(score)), _lib.ptr(ds),
+              float(target if target is not None else 0.0), N, hw[4], hw[5], _lib.ptr(loss), _lib.ptr(dz),
+              _lib.ptr(dwf), _lib.ptr(dbf), _lib.ptr(dy3), st)
+    _lib.call("dl4ss_disc_conv64_bwd", prec, _lib.ptr(y2), _lib.ptr(y3), _lib.ptr(dy3), _lib.ptr(w3), N, hw[2], hw[3],
+              _lib.ptr(dy2), _lib.ptr(dw3), _lib.ptr(db3), _lib.ptr(ws), wsn, st)
+    _lib.call("dl4ss_disc_conv64_bwd", prec, _lib.ptr(y1), _lib.ptr(y2), _lib.ptr(dy2), _lib.ptr(w2), N, hw[0], hw[1],
+              _lib.ptr(dy1), _lib.ptr(dw2), _lib.ptr(db2), _lib.ptr(ws), wsn, st)
+    dx = torch.empty_like(spec) if need_dx else None
+    _lib.call("dl4ss_disc_conv1_bwd", prec, _lib.ptr(spec), _lib.ptr(y1), _lib.ptr(dy1), _lib.ptr(w1), N, T, F,
+              _lib.ptr(dx), _lib.ptr(dw1), _lib.ptr(db1), _lib.ptr(ws), wsn, st)
+    out = (dx, dw1, db1, dw2, db2, dw3, db3, dwf, dbf.view(1))
+    return out if dscore is not None else out + (loss[0],)
+
+
+class DiscriminatorFn(torch.autograd.Function):
+    """The reference's Discriminator (TDAA_beta/main_run_sstune_dis.py:318-336): three Conv2d(., 64, 3x3,
+    stride 2) + ReLU on spec (N, T, F), Linear(64 H3 W3, 1) + sigmoid -> score (N, 1).  Parameters in the
+    reference's layouts: cnn*.weight (64, Cin, 3, 3), final.weight (1, 64 H3 W3) in (c, h, w) order.  The input
+    gradient (the generator's adversarial gradient) is computed only when spec requires it."""
+
+    @staticmethod
+    def forward(ctx, spec, w1, b1, w2, b2, w3, b3, wf, bf, precision):
+        spec = _c(spec.float())
+        score, y1, y2, y3 = disc_fwd_impl(spec, w1, b1, w2, b2, w3, b3, wf, bf, precision)
+        ctx.save_for_backward(spec, _c(w1), _c(w2), _c(w3), _c(wf), score, y1, y2, y3)
+        ctx.precision = precision
+        return score
+
+    @staticmethod
+    def backward(ctx, dscore):
+        spec, w1, w2, w3, wf, score, y1, y2, y3 = ctx.saved_tensors
+        dx, dw1, db1, dw2, db2, dw3, db3, dwf, dbf = disc_bwd_impl(dscore, spec, w1, w2, w3, wf, score, y1, y2, y3,
+                                                                   ctx.precision, bool(ctx.needs_input_grad[0]))
+        return dx, dw1, db1, dw2, db2, dw3, db3, dwf.view_as(wf), dbf, None

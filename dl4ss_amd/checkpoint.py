@@ -96,6 +96,35 @@ def save_reference_classifier(cnet, path):
     return path
 
 
+DIS_KEYS = ("cnn.weight", "cnn.bias", "cnn1.weight", "cnn1.bias", "cnn2.weight", "cnn2.bias", "final.weight",
+            "final.bias")
+
+
+def load_reference_discriminator(module, path):
+    """The reference's ``param_{tag}_dislayer_{epoch}`` file (main_run_sstune_dis.py:661-662: the
+    Discriminator's plain ``state_dict``) into a ``myNet.Discriminator`` (in place).  The file must hold
+    exactly the reference's eight keys with the module's shapes: a file saved at another map size
+    (``final.weight`` is (1, 64 H3 W3)) raises instead of loading partly."""
+    sd = load_state(path)
+    if set(sd) != set(DIS_KEYS):
+        raise KeyError(f"{path}: keys {sorted(sd)} are not the Discriminator's {list(DIS_KEYS)}")
+    own = module.state_dict()
+    for k in DIS_KEYS:
+        if tuple(sd[k].shape) != tuple(own[k].shape):
+            raise ValueError(f"{path}: {k} has shape {tuple(sd[k].shape)}, the module expects {tuple(own[k].shape)}")
+    module.load_state_dict({k: sd[k].to(torch.float32) for k in DIS_KEYS})
+    return module
+
+
+def save_reference_discriminator(module, tag, epoch, directory="params"):
+    """Write ``param_{tag}_dislayer_{epoch}`` as the reference does (dis.py:661-662): the module's
+    state_dict on the CPU.  Round-trips through ``load_reference_discriminator``."""
+    os.makedirs(directory, exist_ok=True)
+    p = os.path.join(directory, f"param_{tag}_dislayer_{epoch}")
+    torch.save({k: v.detach().cpu().clone() for k, v in module.state_dict().items()}, p)
+    return p
+
+
 def save_reference_params(net, directory, tag, epoch):
     """Write the reference's file layout ``param_{tag}_{hidden3d,emblayer,adjlayer}_{epoch}``, and
     ``param_{tag}_attlayer_{epoch}`` for a net that has the 'align' attention weights."""

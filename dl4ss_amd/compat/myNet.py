@@ -13,6 +13,7 @@ reference ``state_dict`` keys load unchanged) and forward semantics follow:
                          cRM:390-406 (width 2E)
   ADDJUST                EvalVer.py:363-377, cRM:408-426
   ATTENTION              EvalVer.py:199-242 ('dot' and 'align'), cRM:247-271 (cRM 'dot' branch)
+  Discriminator          EvalVer.py:328-346, main_run_sstune_dis.py:318-336
   top_k_mask             main_run.py:340-355, EvalVer.py:390-405
 
 Forward and backward of the recurrence, every Linear / GEMM, the attention, the
@@ -37,7 +38,7 @@ except ImportError:  # imported by its bare name (compat.install())
     import config
 
 __all__ = ['Inception3', 'inception_v3', 'BiRNN', 'MIX_SPEECH', 'MIX_SPEECH_classifier', 'SPEECH_EMBEDDING',
-           'ADDJUST', 'ATTENTION', 'top_k_mask']
+           'ADDJUST', 'ATTENTION', 'Discriminator', 'top_k_mask']
 
 
 try:  # Torch_multi/myNet.py:17-330: the VIDEO_QUERY image net (off the audio path; plain torch)
@@ -200,6 +201,36 @@ class ATTENTION(nn.Module):
             return mask.view(B, shp[1], shp[2])
         mask = ag.AttentionDotFn.apply(V, q, self.crm)
         return mask.view(B, shp[1], shp[2], 2) if self.crm else mask.view(B, shp[1], shp[2])
+
+
+class Discriminator(nn.Module):
+    """The adversarial Discriminator (TDAA_beta/main_run_sstune_dis.py:318-336, the same class in
+    main_run_sstune_EvalVer.py:328-346): cnn = Conv2d(1, 64, 3x3, stride 2), cnn1 / cnn2 = Conv2d(64, 64, 3x3,
+    stride 2), ReLU after each, final = Linear(64 H3 W3, 1), sigmoid.  forward(spec (bs, topk, len, fre)) ->
+    score (bs topk, 1).  The reference hard-codes Linear(36480, 1), the (313, 129) map; here the size follows
+    the constructor's (mix_speech_len, speech_fre), whose defaults give that constant.  The submodules hold
+    the parameters under the reference's names (a ``_dislayer_`` state_dict loads unchanged, torch's default
+    initialisation) and are never called: forward and backward run on the HIP kernels (``ag.DiscriminatorFn``).
+    The reference's ``print``s are dropped."""
+
+    def __init__(self, mix_speech_len=313, speech_fre=129, precision=None):
+        super().__init__()
+        self.mix_speech_len, self.speech_fre, self.precision = mix_speech_len, speech_fre, precision
+        feat, _ = ag.disc_dims(mix_speech_len, speech_fre)
+        self.cnn = nn.Conv2d(1, 64, (3, 3), stride=(2, 2))
+        self.cnn1 = nn.Conv2d(64, 64, (3, 3), stride=(2, 2))
+        self.cnn2 = nn.Conv2d(64, 64, (3, 3), stride=(2, 2))
+        self.final = nn.Linear(feat, 1)
+
+    def forward(self, spec):
+        bs, topk, len_, fre = spec.size()
+        if (len_, fre) != (self.mix_speech_len, self.speech_fre):
+            raise ValueError(f"Discriminator built for ({self.mix_speech_len}, {self.speech_fre}) maps, got "
+                             f"({len_}, {fre})")
+        prec = self.precision or getattr(config, "PRECISION", "fp32")
+        return ag.DiscriminatorFn.apply(spec.reshape(bs * topk, len_, fre), self.cnn.weight, self.cnn.bias,
+                                        self.cnn1.weight, self.cnn1.bias, self.cnn2.weight, self.cnn2.bias,
+                                        self.final.weight, self.final.bias, prec)
 
 
 def top_k_mask(batch_pro, alpha, top_k):

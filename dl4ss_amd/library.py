@@ -27,6 +27,9 @@ w_hh, b_hh, cell, H, precision)``      main_run.py:263-273); returns (out, hprev
 ``dl4ss::attention_align(V, q, W1,     ATTENTION 'align' mask (EvalVer.py:228-239,
 W2, w3)``                              DL4SS_Keras/extend_layers.py:50-64)
 ``dl4ss::top_k_mask(p, alpha, k)``     top_k_mask (EvalVer.py:390-405)
+``dl4ss::discriminator(spec, w1, b1,   Discriminator: 3 x (Conv2d 3x3 stride 2 + ReLU), Linear,
+w2, b2, w3, b3, wf, bf, precision)``   sigmoid (main_run_sstune_dis.py:318-336); returns
+                                       (score, y1, y2, y3)
 =====================================  ==========================================================
 
 ``birnn_layer`` returns its saved activations as extra outputs (a custom op cannot stash
@@ -303,6 +306,57 @@ def _(prob, alpha, top_k):
             prob.new_empty(B, dtype=torch.int32))
 
 
+# --------------------------------------------------------------------------- Discriminator
+@_op("discriminator")
+def discriminator(spec: Tensor, w1: Tensor, b1: Tensor, w2: Tensor, b2: Tensor, w3: Tensor, b3: Tensor, wf: Tensor,
+                  bf: Tensor, precision: str) -> Tuple[Tensor, Tensor, Tensor, Tensor]:
+    """spec (N, T, F) -> (score (N, 1), y1, y2, y3); the channels-last activations are saved state."""
+    return ag.disc_fwd_impl(spec, w1, b1, w2, b2, w3, b3, wf, bf, precision)
+
+
+@discriminator.register_fake
+def _(spec, w1, b1, w2, b2, w3, b3, wf, bf, precision):
+    N, T, F = spec.shape
+    _, hw = ag.disc_dims(T, F)
+    act = dict(dtype=ag._disc_act_dtype(precision))
+    return (spec.new_empty(N, 1, **F32),) + tuple(spec.new_empty(N, hw[2 * l], hw[2 * l + 1], 64, **act)
+                                                  for l in range(3))
+
+
+@_op("discriminator_bwd")
+def discriminator_bwd(dscore: Tensor, spec: Tensor, w1: Tensor, w2: Tensor, w3: Tensor, wf: Tensor, score: Tensor,
+                      y1: Tensor, y2: Tensor, y3: Tensor, precision: str, need_dx: bool
+                      ) -> Tuple[Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor]:
+    out = ag.disc_bwd_impl(dscore, spec, w1, w2, w3, wf, score, y1, y2, y3, precision, need_dx)
+    return ((out[0] if out[0] is not None else spec.new_empty(0)),) + tuple(out[1:])
+
+
+@discriminator_bwd.register_fake
+def _(dscore, spec, w1, w2, w3, wf, score, y1, y2, y3, precision, need_dx):
+    b = lambda: spec.new_empty(64, **F32)  # noqa: E731
+    return ((torch.empty_like(spec, **F32) if need_dx else spec.new_empty(0, **F32)), torch.empty_like(w1, **F32), b(),
+            torch.empty_like(w2, **F32), b(), torch.empty_like(w3, **F32), b(), torch.empty_like(wf, **F32),
+            spec.new_empty(1, **F32))
+
+
+def _disc_setup(ctx, inputs, output):
+    spec, w1, b1, w2, b2, w3, b3, wf, bf, precision = inputs
+    score, y1, y2, y3 = output
+    ctx.mark_non_differentiable(y1, y2, y3)
+    ctx.save_for_backward(spec, w1, w2, w3, wf, score, y1, y2, y3)
+    ctx.precision = precision
+
+
+def _disc_backward(ctx, dscore, _dy1, _dy2, _dy3):
+    spec, w1, w2, w3, wf, score, y1, y2, y3 = ctx.saved_tensors
+    need = bool(ctx.needs_input_grad[0])
+    out = discriminator_bwd(dscore.contiguous(), spec, w1, w2, w3, wf, score, y1, y2, y3, ctx.precision, need)
+    return ((out[0] if need else None),) + tuple(out[1:]) + (None,)
+
+
+discriminator.register_autograd(_disc_backward, setup_context=_disc_setup)
+
+
 OPS = ("stft_mag", "stft_complex", "istft", "istft_apply", "mix_sources", "birnn_layer", "birnn_layer_bwd",
        "linear_tanh", "linear_tanh_bwd", "attention_dot", "attention_dot_bwd", "attention_align",
-       "attention_align_bwd", "top_k_mask")
+       "attention_align_bwd", "top_k_mask", "discriminator", "discriminator_bwd")

@@ -478,6 +478,45 @@ int dl4ss_cls_head_fwd(const float* m, const float* W, const float* b, int B, in
 int dl4ss_cls_head_loss_bwd(const float* p, const float* y, const float* m, const float* W, int B, int D, int C,
                             int T, float* loss, float* dz, float* dW, float* db, float* dOut_bcast, void* stream);
 
+/* ---- Discriminator (TDAA_beta/main_run_sstune_dis.py:318-336,615-647; the same class in
+ * main_run_sstune_EvalVer.py:328-346): Conv2d(1, 64, 3x3, stride 2) + two Conv2d(64, 64, 3x3, stride 2),
+ * ReLU after each, Linear(64 H3 W3, 1) + sigmoid, MSE against 1 / 0, and their autograd.
+ * Activations are channels-last (N, H, W, 64), fp32 (prec 0) or bf16 (prec 1); parameters and their
+ * gradients are fp32 in the reference's layouts (conv weight (64, Cin, 3, 3), final.weight flattened
+ * (c, h, w)).  Hout = (Hin - 3) / 2 + 1 per layer and axis.  No float atomics: two calls on the same
+ * inputs agree bit for bit.  Sizes are checked before any device call. */
+/* hw = {H1, W1, H2, W2, H3, W3} of a (T, F) map; returns the feature count 64 H3 W3, or -1 when the map is
+ * smaller than 15 x 15.  Host only (hw may be NULL). */
+int dl4ss_disc_dims(int T, int F, int hw[6]);
+/* Bytes of the workspace the *_bwd calls of N maps of (T, F) share (split-K partials of the largest
+ * layer), or -1 for an unsupported size.  Host only. */
+long long dl4ss_disc_ws_bytes(int N, int T, int F);
+/* x (N, T, F) fp32, w (64, 1, 3, 3), b (64) -> y1 (N, H1, W1, 64) = relu(conv + b); fp32 arithmetic, the
+ * output alone is rounded in bf16. */
+int dl4ss_disc_conv1_fwd(int prec, const float* x, const float* w, const float* b, int N, int T, int F, void* y1,
+                         void* stream);
+/* x (N, Hin, Win, 64), w (64, 64, 3, 3), b (64) -> y (N, Hout, Wout, 64) = relu(conv + b): implicit GEMM on
+ * the MFMA (M = N Hout Wout, N = 64, K = 576), rows gathered from the nine taps. */
+int dl4ss_disc_conv64_fwd(int prec, const void* x, const float* w, const float* b, int N, int Hin, int Win, void* y,
+                          void* stream);
+/* y3 (N, H3, W3, 64), wf (64 H3 W3), bf (1) -> z (N), score (N) = sigmoid(z) */
+int dl4ss_disc_head_fwd(int prec, const void* y3, const float* wf, const float* bf, int N, int H3, int W3, float* z,
+                        float* score, void* stream);
+/* Head backward.  dscore (N) given: dz = dscore s (1 - s).  dscore NULL: the fused loss
+ * loss[0] = mean_n (score_n - target)^2 (dis.py:622-624,642) and its gradient.  Writes dz (N), dwf, dbf (1)
+ * and dy3 (N, H3, W3, 64) in the activation type; loss may be NULL. */
+int dl4ss_disc_head_bwd(int prec, const void* y3, const float* wf, const float* score, const float* dscore,
+                        float target, int N, int H3, int W3, float* loss, float* dz, float* dwf, float* dbf, void* dy3,
+                        void* stream);
+/* 64 -> 64 layer backward from dy and the saved post-ReLU y (gate y > 0 applied on load): dw (64, 64, 3, 3),
+ * db (64) and, when dx is not NULL, dx (N, Hin, Win, 64) with every element written (exact zeros where no
+ * window reaches).  ws / ws_bytes: dl4ss_disc_ws_bytes of the network this layer belongs to. */
+int dl4ss_disc_conv64_bwd(int prec, const void* x, const void* y, const void* dy, const float* w, int N, int Hin,
+                          int Win, void* dx, float* dw, float* db, void* ws, long long ws_bytes, void* stream);
+/* conv1 backward: dw (64, 1, 3, 3), db (64) and, when dx is not NULL, the input-map gradient dx (N, T, F) fp32. */
+int dl4ss_disc_conv1_bwd(int prec, const float* x, const void* y1, const void* dy1, const float* w, int N, int T,
+                         int F, float* dx, float* dw, float* db, void* ws, long long ws_bytes, void* stream);
+
 /* ---- BSS-eval (replaces the un-vendored separation.bss_eval_sources of
  *      Torch_multi/bss_test.py:5,55 -- BSS_EVAL v3, 512-tap distortion filters) ---- */
 /* R (M,P,P,L) fp64: R[m][a][b][l] = sum_n x[m][a][n] x[m][b][n+l], l < L, x (M,P,N) fp32
