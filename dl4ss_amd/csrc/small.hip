@@ -86,7 +86,8 @@ __global__ __launch_bounds__(64) void query_fwd_kernel(const float* __restrict__
   for (int k = 0; k < KMAX; ++k) {
     if (k >= Kg) break;
     const float r = wave_sum(acc[k]);
-    if (lane == 0) q[((long long)b * K + k) * W + o] = (id[k] >= 0 ? emb[(long long)id[k] * W + o] : 0.0f) + r;
+    // no speaker (id -1): a zero query, also with ADDJUST (the mean part in r belongs to no speaker)
+    if (lane == 0) q[((long long)b * K + k) * W + o] = id[k] >= 0 ? emb[(long long)id[k] * W + o] + r : 0.0f;
   }
 }
 
@@ -94,19 +95,22 @@ __global__ __launch_bounds__(64) void query_fwd_kernel(const float* __restrict__
 //   dh_bcast[b][c] = sum_o W[o][c] u[b][o] / T,   u[b][o] = sum_k dq[b,k,o]   (c < D)
 //   dEmb[idx[b,k]][c] += dq[b,k,c] + sum_o W[o][D + c] dq[b,k,o]
 //   dW_adj[o][c] += sum_b u[b][o] mean[b][c]  (c < D);  sum_{b,k} dq[b,k,o] Emb[idx[b,k]][c-D]
+// A row with idx -1 (no speaker) has a zero query whatever h and W_adj are: its dq is left out of u (and
+// of every other sum).
 // Every element has one owner thread and a fixed summation order (no atomics).  Round 6: each role's
 // loads of a QCH-term chunk are issued together from clamped addresses and folded by selects (no
 // branches): the round-5 loops (five or eight loads at a time, predicated loads compiled to branches)
 // left four to ten dependent load rounds per role on this ~14 us launch.
 constexpr int QCH = 32;  // terms per load chunk (a multiple of 8: dW_adj's accumulator of term b is b & 7)
 __device__ __forceinline__ void query_bwd_dh(int bx, int by, float* su, const float* __restrict__ dq,
-                                             const float* __restrict__ wadj, int T, int D, int K, int W,
+                                             const int* __restrict__ idx, const float* __restrict__ wadj, int T,
+                                             int D, int K, int W,
                                              float* __restrict__ dh_bcast) {
   const int b = by, c = bx * 64 + threadIdx.x;
   const float* dqb = dq + (long long)b * K * W;
   for (int o = threadIdx.x; o < W; o += 64) {  // u[b][o], k in order from zero
     float u = 0.f;
-    for (int k = 0; k < K; ++k) u += dqb[k * W + o];
+    for (int k = 0; k < K; ++k) u = idx[b * K + k] >= 0 ? u + dqb[k * W + o] : u;
     su[o] = u;
   }
   __syncthreads();
@@ -195,7 +199,7 @@ __device__ __forceinline__ void query_bwd_w(int bx, int by, float* sm, const flo
   __syncthreads();
   for (int b = threadIdx.x; b < B; b += 64) {
     float u = 0.f;
-    for (int k = 0; k < K; ++k) u += sdq[b * K + k];
+    for (int k = 0; k < K; ++k) u = sid[b * K + k] >= 0 ? u + sdq[b * K + k] : u;
     su[b] = u;
   }
   __syncthreads();
@@ -269,7 +273,7 @@ __global__ __launch_bounds__(64) void query_bwd_kernel(QbArgs a) {
   }
   blk -= a.n_emb + a.n_zero;
   if (blk < a.n_dh) {
-    query_bwd_dh(blk % a.n_dh_x, blk / a.n_dh_x, sm, a.dq, a.wadj, a.T, a.D, a.K, a.W, a.dh);
+    query_bwd_dh(blk % a.n_dh_x, blk / a.n_dh_x, sm, a.dq, a.idx, a.wadj, a.T, a.D, a.K, a.W, a.dh);
     return;
   }
   blk -= a.n_dh;

@@ -173,7 +173,9 @@ enum { DL4SS_CELL_LSTM = 0, DL4SS_CELL_GRU = 1 };
 #define DL4SS_RNN_WS_ZEROED 0x100
 /* precision flag of dl4ss_birnn_bwd_ex: dGh_bf16 is laid out (B, T, 2, pad8(NGATE*H)) -- each
  * direction's columns start 16-B aligned (the GRU's 900 gate rows -> 904), so both directions'
- * dW_hh run as one LDS-DMA batched GEMM (gemm_gl).  The unpadded default is (B, T, 2, NGATE*H). */
+ * dW_hh run as one LDS-DMA batched GEMM (gemm_gl).  The unpadded default is (B, T, 2, NGATE*H).  The pad
+ * columns (900..903 of each direction at H = 300) are NOT written (as the M extent of a k-major gemm_gl
+ * operand they never reach a result). */
 #define DL4SS_RNN_DGH_PAD8 0x200
 /* precision flag of dl4ss_birnn_bwd_ex (bf16 BPTT with fused bias gradients): leave the per-row
  * bias partials in the workspace; dl4ss_birnn_bias_reduce adds those of n launches (n <= 8, their
@@ -277,7 +279,8 @@ int dl4ss_birnn_bwd(int cell, int precision, int B, int T, int H, const float* d
 /* dl4ss_birnn_bwd with bf16 extras (precision 1, packed-hand-off kernel only): dG_bf16 /
  * dGh_bf16 (B,T,2,NG*H) receive bf16 copies (the weight-gradient / dX GEMM operands),
  * dG / dGh may then be NULL, and db_ih / db_hh (2, NG*H) are ACCUMULATED with the sums
- * over (b,t) of dG / dGh (the bias gradients; fp32 atomics, one per cell and gate).
+ * over (b,t) of dG / dGh (the bias gradients: each cell's sum over t in step order goes to a per-row
+ * partial in the workspace, a fixed-order reduce adds the rows -- no atomics, bitwise repeatable).
  * Large hidden sizes (320 < H <= 640; H > 640 is refused before any device call): the BPTT of the
  * H = 600 speaker classifier, loss.backward() through nn.LSTM(129, 600, 3, bidirectional) at
  * Torch_multi/test_multi_labels_speech.py:444 (:240-246).  Generic kernel only (precision 0 or 1, both
@@ -334,7 +337,9 @@ int dl4ss_loss_finalize(const float* part_loss, int B, int K, int nblk, const in
 
 /* ---- speaker queries, reductions, optimizer ------------------------------ */
 /* q[b,k] = Emb[idx[b,k]] (+ W_adj [mean_t h[b]; Emb[idx[b,k]]]); h (B,T,D).
- * SPEECH_EMBEDDING + ADDJUST: EvalVer.py:348-377,606-608. w_adj may be NULL; an idx of -1 (no speaker) gives a zero query.
+ * SPEECH_EMBEDDING + ADDJUST: EvalVer.py:348-377,606-608. w_adj may be NULL; an idx of -1 (no speaker) gives a zero
+ * query, with w_adj too (the W_adj . mean part belongs to no speaker), and its dq reaches no gradient of
+ * dl4ss_query_bwd[_ex] (d_emb, d_wadj or dh_bcast).
  * mean_out (B,D) receives mean_t h; with h NULL it is instead READ as that mean, formed by the
  * recurrence (dl4ss_birnn_fwd_xw_ex h_mean). */
 int dl4ss_query_fwd(const float* h, int B, int T, int D, const int* idx, const float* emb, const float* w_adj, int K,
