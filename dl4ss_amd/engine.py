@@ -234,7 +234,7 @@ class SepTrainer:
         # in front of every recurrence launch.  Zeroed once: a launch that completes leaves its
         # workspace fit for the next launch of the same shape (T >= 4: no stale tag can match, and
         # the packed kernels put their start counters / placement granules back, release_start in
-        # birnn.hip), so there is no per-step fill (round 5, 10.4 us); check() zeroes it again after
+        # birnn_common.h), so there is no per-step fill (round 5, 10.4 us); check() zeroes it again after
         # a timed-out launch, whose half-written hand-offs could.  DL4SS_WS_FILL=1: the fill per step.
         w8 = (ws + 255) // 256 * 32
         self.rnn_ws_all = torch.zeros(2, net.L * w8, device=dev, dtype=torch.int64)  # [fwd | bwd][layer]
@@ -286,7 +286,7 @@ class SepTrainer:
         # Forward input projections x W_ih^T + b_ih formed inside the packed recurrence kernel
         # (dl4ss_birnn_fwd_xw) instead of a gemm_gl launch + a G buffer round trip; bitwise the same
         # G (tests/test_rnn_xw_gpu.py).  Each tile's projection of a block of 16 / BC steps is one
-        # MFMA chain, split one part per step over the waves with slack (birnn.hip).  DL4SS_RNN_XW:
+        # MFMA chain, split one part per step over the waves with slack (birnn_fwd_pk.hip).  DL4SS_RNN_XW:
         # "1" (default) every layer (C2, per launch: 600-wide layers 351 us vs 328 + 52 us for
         # recurrence + GEMM, first layer 313 vs 328 + 30), "l0" the first layer only, "0" none.
         xw = os.environ.get("DL4SS_RNN_XW", "1")

@@ -6,7 +6,7 @@ section 8f f1).
   ``TDAA_beta/main_run_sstune_EvalVer.py:305-326``): BiLSTM(129, 600, 3 layers) -> mean over t ->
   Linear(1200, N_lab) -> sigmoid.  Flat fp32 parameters under the reference ``state_dict``
   names (``layer.weight_ih_l0``, ..., ``Linear.weight``), so a reference checkpoint loads
-  directly.  Its H = 600 recurrence runs the forward-only large-H plan of ``birnn.hip``.
+  directly.  Its H = 600 recurrence runs the forward-only large-H plan of ``birnn_fwd.hip``.
 * ``MaskNetForward`` -- ``MIX_SPEECH`` forward only (V = tanh(Linear(BiRNN(X)))) on a ``SepNet``.
 * ``RecursiveExtractor`` -- the recursive extraction loop of ``GRID.py:383-475`` (SURVEY section
   3 (E)): classifier -> on-device choice of the first not-yet-extracted speaker among the

@@ -1,6 +1,6 @@
-"""LDS bank-conflict model of the packed recurrence kernels' per-step LDS accesses (birnn.hip,
-rnn_fwd_pk_kernel / rnn_bwd_pk_kernel) at the C2 plan (BiLSTM, B = 32, H = 300: BC = 4, J = 20,
-NG = 15) and the BiGRU plan, from the lane groups and bank functions of
+"""LDS bank-conflict model of the packed recurrence kernels' per-step LDS accesses (birnn_fwd_pk.hip /
+birnn_bwd_pk.hip, rnn_fwd_pk_kernel / rnn_bwd_pk_kernel; region layouts: birnn_layout.h) at the C2 plan
+(BiLSTM, B = 32, H = 300: BC = 4, J = 20, NG = 15) and the BiGRU plan, from the lane groups and bank functions of
 MI355X_MICROARCH.md section LDS (the table of lane groups per instruction).
 
 For every access of a step: LDS-array cycles, the conflict-free minimum, and the extra

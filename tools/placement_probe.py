@@ -1,7 +1,7 @@
 """Diagnostic: how the persistent recurrence's workgroups were spread over the XCDs in a training step.
 
 Each packed-kernel launch counts its workgroups per XCD in the group-formation counters at the end of
-its hand-off workspace (birnn.hip group_pk: 8 per-XCD counters + the overflow count).  Runs a few graph
+its hand-off workspace (birnn_common.h group_pk: 8 per-XCD counters + the overflow count).  Runs a few graph
 steps of the C2 workload and prints, for every (pass, layer) workspace of the last step, the per-XCD
 counts and how many workgroups overflowed their XCD (their groups span XCDs: write-through hand-offs).
 

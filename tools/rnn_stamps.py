@@ -63,7 +63,7 @@ def main():
         tr.backward()
         torch.cuda.synchronize()
         bw = stamps.view(240, 16).double().cpu() / T
-    # slot i = cycles from the previous stamp to STAMP(i) (birnn.hip): forward cell waves
+    # slot i = cycles from the previous stamp to STAMP(i) (birnn_fwd_pk.hip / birnn_bwd_pk.hip): forward cell waves
     # B2 -> gates (5) -> publish store issued (6) -> saved-state stores (4); BPTT cell waves
     # B2 -> MFMA + transpose (4) -> granule publish (5) -> dG stores (6); BPTT cell phase B1 ->
     # operand / partial-sum reads (7) -> math and the bf16 dgh image (2)

@@ -1,8 +1,6 @@
 """Top-layer BPTT launch alone (C2 shape: B = 32, T = 251, H = 300, BiLSTM, bf16 packed) reading dOut as S
-split-K slabs, us per launch (HIP events, median of 5 x 5 launches), for S = 1..4 and slab strides padded by
-PAD floats (a probe build with -DDL4SS_EXP_ZS_PAD reads DL4SS_EXP_ZS_PAD per process: run once per pad)."""
+split-K slabs, us per launch (HIP events, median of 5 x 5 launches), for S = 1..4."""
 import json
-import os
 import statistics
 import sys
 
@@ -14,7 +12,6 @@ from dl4ss_amd import _lib  # noqa: E402
 dev = torch.device("cuda")
 B, T, H = 32, 251, 300
 NGH = 4 * H
-PAD = int(os.environ.get("DL4SS_EXP_ZS_PAD", "0"))
 g = torch.Generator().manual_seed(0)
 G = (torch.randn(B, T, 2, NGH, generator=g) * 0.5).to(dev)
 whh = (torch.randn(2, NGH, H, generator=g) / H ** 0.5).to(dev)
@@ -29,7 +26,7 @@ st = torch.zeros(1, dtype=torch.int32, device=dev)
 _lib.call("dl4ss_birnn_fwd", 0, 1, B, T, H, _lib.ptr(G), _lib.ptr(whh), _lib.ptr(bhh), _lib.ptr(o), _lib.ptr(hp),
           _lib.ptr(act), _lib.ptr(cs), _lib.ptr(wsb), ws, _lib.ptr(st), _lib.stream_ptr())
 torch.cuda.synchronize()
-zs = B * T * 2 * H + PAD
+zs = B * T * 2 * H
 sl = torch.randn(4 * zs, generator=g).to(dev)
 dGb = torch.empty(B * T, 2 * NGH, device=dev, dtype=torch.bfloat16)
 dbi = torch.zeros(2 * NGH, device=dev)
@@ -56,4 +53,4 @@ for S in (1, 2, 3, 4):
         torch.cuda.synchronize()
         ts.append(a.elapsed_time(b) * 1e3 / 5)
     assert int(st.item()) == 0
-    print(json.dumps({"S": S, "pad_floats": PAD, "us": round(statistics.median(ts), 1)}), flush=True)
+    print(json.dumps({"S": S, "us": round(statistics.median(ts), 1)}), flush=True)

@@ -13,9 +13,10 @@ from dl4ss_amd import build as B  # noqa: E402
 
 
 def main(tag, defs):
-    """--minimal: recompile only birnn.hip, with -DRNN_EXP_MINIMAL (the packed BC = 4 kernels of the
-    C2 / C4 step at B = 32 only), and link it with the shipped build's other objects (python -m
-    dl4ss_amd.build first): a recurrence variant in well under a minute."""
+    """--minimal: recompile only the packed recurrence kernels (birnn_fwd_pk.hip, birnn_bwd_pk.hip), with
+    -DRNN_EXP_MINIMAL (their BC = 4 instantiations, the C2 / C4 step at B = 32, only), and link them
+    with the shipped build's other objects (python -m dl4ss_amd.build first): a recurrence variant in
+    well under a minute.  --only=birnn_bwd_pk.hip alone rebuilds the whole packed BPTT in about that."""
     od = f"/tmp/variant_obj_{tag}"
     os.makedirs(od, exist_ok=True)
     srcs = sorted(f for f in os.listdir(B.CSRC) if f.endswith(".hip"))
@@ -24,7 +25,7 @@ def main(tag, defs):
         defs = [d for d in defs if d != "--minimal"] + ["-DRNN_EXP_MINIMAL"]
     # --only=a.hip,b.hip: recompile just those sources, link the shipped build's other objects
     only = [d.split("=", 1)[1].split(",") for d in defs if d.startswith("--only=")]
-    only = only[0] if only else (["birnn.hip"] if minimal else None)
+    only = only[0] if only else (["birnn_fwd_pk.hip", "birnn_bwd_pk.hip"] if minimal else None)
     defs = [d for d in defs if not d.startswith("--only=")] + ["-DDL4SS_VARIANT_BUILD"]
 
     def comp(f):
