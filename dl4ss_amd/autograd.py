@@ -13,9 +13,7 @@ import ctypes
 import torch
 
 from . import _lib, ops
-
-CELLS = {"lstm": 0, "gru": 1}
-LARGE_H = 320  # hidden sizes above it run dl4ss_birnn_bwd_ex's large-hidden BPTT (up to 640)
+from .ops import CELLS
 
 
 def _c(t):
@@ -43,9 +41,8 @@ def birnn_fwd_impl(x, w_ih, b_ih, w_hh, b_hh, cell, H, precision):
     wsn = _birnn_ws_bytes(cid, B, H)
     ws = torch.empty((wsn + 7) // 8, dtype=torch.int64, device=dev)
     status = torch.zeros(1, dtype=torch.int32, device=dev)
-    _lib.call("dl4ss_birnn_fwd", cid, ops.PREC[precision], B, T, H, _lib.ptr(G), _lib.ptr(_c(w_hh)),
-              _lib.ptr(_c(b_hh)), _lib.ptr(out), _lib.ptr(hprev), _lib.ptr(act),
-              _lib.ptr(cs) if cs is not None else None, _lib.ptr(ws), wsn, _lib.ptr(status), _lib.stream_ptr())
+    ops.birnn_fwd(cell, B, T, H, G=G, w_hh=_c(w_hh), b_hh=_c(b_hh), out=out, hprev=hprev, act=act, cs=cs, ws=ws,
+                  ws_bytes=wsn, status=status, precision=precision)
     _check_status(status, "dl4ss_birnn_fwd")
     return out, hprev, act, cs
 
@@ -68,14 +65,9 @@ def birnn_bwd_impl(dout, x, w_ih, w_hh, hprev, act, cs, cell, H, precision, need
     dGh = torch.empty_like(dG) if cell == "gru" else None
     ws = torch.empty((wsn + 7) // 8, dtype=torch.int64, device=dev)
     status = torch.zeros(1, dtype=torch.int32, device=dev)
-    bptt = (CELLS[cell], ops.PREC[precision], B, T, H, _lib.ptr(dout), None, _lib.ptr(_c(w_hh)), _lib.ptr(act),
-            _lib.ptr(cs) if cell == "lstm" else None, _lib.ptr(hprev), _lib.ptr(dG),
-            _lib.ptr(dGh) if dGh is not None else None)
-    if H > LARGE_H:  # the H = 600 classifier: the large-hidden BPTT (generic kernel, no bf16 extras)
-        _lib.call("dl4ss_birnn_bwd_ex", *bptt, None, None, None, None, _lib.ptr(ws), wsn, _lib.ptr(status),
-                  _lib.stream_ptr())
-    else:
-        _lib.call("dl4ss_birnn_bwd", *bptt, _lib.ptr(ws), wsn, _lib.ptr(status), _lib.stream_ptr())
+    # (one entry point for every H: the H = 600 classifier runs its large-hidden BPTT, the generic kernel)
+    ops.birnn_bwd(cell, B, T, H, dOut=dout, w_hh=_c(w_hh), act=act, cs=cs if cell == "lstm" else None, hprev=hprev,
+                  dG=dG, dGh=dGh, ws=ws, ws_bytes=wsn, status=status, precision=precision)
     _check_status(status, "dl4ss_birnn_bwd")
     dGh = dG if dGh is None else dGh
     w_ih = _c(w_ih)

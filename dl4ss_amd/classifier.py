@@ -88,10 +88,9 @@ class ClassifierTrainer:
         for l in range(net.L):
             ops.gemm(x, net.cat_view("weight_ih", l), transB=True, bias=net.cat_view("bias_ih", l), out=self.G,
                      precision=self.precision)
-            _lib.call("dl4ss_birnn_fwd", LSTM, ops.PREC[self.precision], B, T, H, _lib.ptr(self.G),
-                      _lib.ptr(net.cat_view("weight_hh", l)), _lib.ptr(net.cat_view("bias_hh", l)),
-                      _lib.ptr(self.out[l]), _lib.ptr(self.hprev[l]), _lib.ptr(self.act[l]), _lib.ptr(self.cs[l]),
-                      _lib.ptr(self.rnn_ws), self.ws_bytes, _lib.ptr(self.status), st)
+            ops.birnn_fwd("lstm", B, T, H, G=self.G, w_hh=net.cat_view("weight_hh", l), b_hh=net.cat_view("bias_hh", l),
+                          out=self.out[l], hprev=self.hprev[l], act=self.act[l], cs=self.cs[l], ws=self.rnn_ws,
+                          ws_bytes=self.ws_bytes, status=self.status, precision=self.precision)
             x = self.out[l].view(B * T, 2 * H)
         _lib.call("dl4ss_time_mean", _lib.ptr(self.out[-1]), B, T, 2 * H, _lib.ptr(self.mean), st)
         _lib.call("dl4ss_cls_head_fwd", _lib.ptr(self.mean), _lib.ptr(net.view("Linear.weight")),
@@ -118,15 +117,13 @@ class ClassifierTrainer:
         net, B, T, H = self.net, self.B, self.T, self.net.H
         BT, NGH = B * T, 4 * H
         g = net.grad
-        st = _lib.stream_ptr()
         dH = self._zero_dout
         for l in range(net.L - 1, -1, -1):
             top = l == net.L - 1
             dG = self.G
-            _lib.call("dl4ss_birnn_bwd_ex", LSTM, ops.PREC[self.precision], B, T, H, _lib.ptr(dH),
-                      _lib.ptr(self.dmb) if top else None, _lib.ptr(net.cat_view("weight_hh", l)),
-                      _lib.ptr(self.act[l]), _lib.ptr(self.cs[l]), _lib.ptr(self.hprev[l]), _lib.ptr(dG), None, None,
-                      None, None, None, _lib.ptr(self.rnn_ws), self.ws_bytes, _lib.ptr(self.status), st)
+            ops.birnn_bwd("lstm", B, T, H, dOut=dH, dOut_bcast=self.dmb if top else None,
+                          w_hh=net.cat_view("weight_hh", l), act=self.act[l], cs=self.cs[l], hprev=self.hprev[l], dG=dG,
+                          ws=self.rnn_ws, ws_bytes=self.ws_bytes, status=self.status, precision=self.precision)
             xl = self.feats.view(BT, -1) if l == 0 else self.out[l - 1].view(BT, 2 * H)
             # unsplit (splitk = 1): no float atomics, the step repeats bit for bit
             ops.gemm(dG, xl, transA=True, out=net.cat_view("weight_ih", l, g), precision=self.precision)

@@ -25,21 +25,8 @@ import math
 import torch
 
 from . import _lib, ops
-from .engine import CELLS, _ngate
-
-
-# split-precision operand images (dl4ss_f32_to_bf16_hilo): [x_hi | x_lo | x_hi] . [w_hi | w_hi | w_lo]
-A_SPLIT, W_SPLIT = 0b010, 0b100
-
-
-def _p8(n):
-    return (n + 7) // 8 * 8
-
-
-def _hilo(x, y, segw, pattern):
-    """y = the three-segment split image of the fp32 rows x (segments of segw, hi / lo by pattern)."""
-    _lib.call("dl4ss_f32_to_bf16_hilo", _lib.ptr(x, True), x.stride(0), x.shape[0], x.shape[1], _lib.ptr(y),
-              y.stride(0), segw, 3, pattern, _lib.stream_ptr())
+from .engine import CELLS, FlatParams, _ngate
+from .ops import A_SPLIT, W_SPLIT, hilo, pad8
 
 
 class _SplitWeights:
@@ -55,9 +42,9 @@ class _SplitWeights:
         if key != self.key:
             self.img, self.key = {}, key
         if name not in self.img:
-            seg = _p8(w.shape[1])
+            seg = pad8(w.shape[1])
             y = torch.empty(w.shape[0], 3 * seg, device=w.device, dtype=torch.bfloat16)
-            _hilo(w, y, seg, W_SPLIT)
+            hilo(w, y, seg, W_SPLIT)
             self.img[name] = y
         return self.img[name]
 
@@ -92,24 +79,22 @@ class _BiRNNStack:
         ``rnn_precision`` (default: the same; "bf16" for bf16s) the recurrent matvec."""
         B, T, H = self.B, self.T, self.H
         rnn_precision = rnn_precision or ("bf16" if precision == "bf16s" else precision)
-        st = _lib.stream_ptr()
         x = x2d
         out = None
         for l in range(self.L):
             if precision == "bf16s":
-                seg = _p8(x.shape[1])
+                seg = pad8(x.shape[1])
                 xs = self._xs(B * T, 3 * seg, x.device)
-                _hilo(x, xs, seg, A_SPLIT)
+                hilo(x, xs, seg, A_SPLIT)
                 ops.gemm_bf16_gl(xs, split_w.get(f"weight_ih_l{l}", cat_view("weight_ih", l)), transB=True,
                                  bias=cat_view("bias_ih", l), out=self.G)
             else:
                 ops.gemm(x, cat_view("weight_ih", l), transB=True, bias=cat_view("bias_ih", l), out=self.G,
                          precision=precision)
             out = self.out[l % 2]
-            _lib.call("dl4ss_birnn_fwd", CELLS[self.cell], ops.PREC[rnn_precision], B, T, H, _lib.ptr(self.G),
-                      _lib.ptr(cat_view("weight_hh", l)), _lib.ptr(cat_view("bias_hh", l)), _lib.ptr(out),
-                      _lib.ptr(self.hprev), _lib.ptr(self.act), _lib.ptr(self.cs) if self.cs is not None else None,
-                      _lib.ptr(self.ws), self.wsn, _lib.ptr(self.status), st)
+            ops.birnn_fwd(self.cell, B, T, H, G=self.G, w_hh=cat_view("weight_hh", l), b_hh=cat_view("bias_hh", l),
+                          out=out, hprev=self.hprev, act=self.act, cs=self.cs, ws=self.ws, ws_bytes=self.wsn,
+                          status=self.status, precision=rnn_precision)
             x = out.view(B * T, 2 * H)
         return out
 
@@ -126,44 +111,16 @@ class _BiRNNStack:
             raise RuntimeError(f"BiRNN hand-off timed out (status {s})")
 
 
-class ClassifierNet:
+class ClassifierNet(FlatParams):
     """Parameters of MIX_SPEECH_classifier, flat fp32 with the reference names."""
 
     def __init__(self, input_fre=129, hidden=600, num_layers=3, num_labels=101, device="cuda", seed=1):
         self.F, self.H, self.L, self.num_labels = input_fre, hidden, num_layers, num_labels
-        NGH = 4 * hidden
-        specs = []
-        for l in range(num_layers):
-            D = input_fre if l == 0 else 2 * hidden
-            for kind, shape in (("weight_ih", (NGH, D)), ("weight_hh", (NGH, hidden)), ("bias_ih", (NGH,)),
-                                ("bias_hh", (NGH,))):
-                specs.append((f"layer.{kind}_l{l}", shape))
-                specs.append((f"layer.{kind}_l{l}_reverse", shape))
+        specs = self._layer_specs(num_layers, input_fre, hidden, 4 * hidden)
         specs += [("Linear.weight", (num_labels, 2 * hidden)), ("Linear.bias", (num_labels,))]
-        self.specs = specs
-        self.offsets = {}
-        off = 0
-        for name, shape in specs:
-            self.offsets[name] = (off, shape)
-            off += (math.prod(shape) + 3) // 4 * 4  # 16-B aligned views
-        self.device = torch.device(device)
-        self.flat = torch.zeros(off, device=self.device, dtype=torch.float32)
+        self._allocate(specs, device)
         self.grad = None  # the flat gradient, same layout: allocated by a ClassifierTrainer on this net
         self.reset_parameters(seed)
-
-    def view(self, name, buf=None):
-        """The parameter ``name``, or its counterpart in ``buf`` (a flat buffer of the same layout:
-        the gradient, an Adam moment)."""
-        off, shape = self.offsets[name]
-        return (self.flat if buf is None else buf)[off:off + math.prod(shape)].view(shape)
-
-    def cat_view(self, kind, l, buf=None):
-        """[fwd; reverse] of layer l (adjacent in the flat buffer by construction)."""
-        a = self.view(f"layer.{kind}_l{l}")
-        off = self.offsets[f"layer.{kind}_l{l}"][0]
-        n = a.numel()
-        v = (self.flat if buf is None else buf)[off:off + 2 * n]
-        return v.view(2 * a.shape[0], *a.shape[1:]) if a.dim() == 2 else v
 
     def named_parameters(self):
         """(name, tensor) pairs as torch's ``named_parameters()`` yields them, under the reference's names, in
@@ -184,13 +141,6 @@ class ClassifierNet:
         for name, shape in self.specs:
             k = 1.0 / math.sqrt(self.H if name.startswith("layer.") else 2 * self.H)
             self.view(name).copy_(torch.empty(shape).uniform_(-k, k, generator=g))
-
-    def load_state_dict(self, sd):
-        for name, _ in self.specs:
-            self.view(name).copy_(sd[name].to(torch.float32))
-
-    def state_dict(self):
-        return {name: self.view(name).detach().clone() for name, _ in self.specs}
 
 
 class ClassifierForward:
@@ -244,9 +194,9 @@ class MaskNetForward:
                                 split_w=self.split_w)
         h2 = self.h.view(B * T, 2 * net.H)
         if self.precision == "bf16s":
-            seg = _p8(2 * net.H)
+            seg = pad8(2 * net.H)
             hs = self.stack._xs(B * T, 3 * seg, h2.device)
-            _hilo(h2, hs, seg, A_SPLIT)
+            hilo(h2, hs, seg, A_SPLIT)
             ops.gemm_bf16_gl(hs, self.split_w.get("mix.Linear.weight", net.view("mix.Linear.weight")), transB=True,
                              bias=net.view("mix.Linear.bias"), epilogue=ops.EPI_TANH, out=out)
             return out

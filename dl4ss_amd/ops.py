@@ -364,6 +364,67 @@ def adam_(p, g, m, v, step, lr=2e-4, betas=(0.9, 0.999), eps=1e-8, status=None, 
               float(gscale), _lib.ptr(loss), _lib.stream_ptr())
 
 
+# ---------------------------------------------------------------------------
+# the bidirectional recurrence
+# ---------------------------------------------------------------------------
+CELLS = {"lstm": 0, "gru": 1}
+# flags OR-ed into the recurrence entry points' precision argument (include/dl4ss_hip.h)
+WS_ZEROED = 0x100  # DL4SS_RNN_WS_ZEROED: the caller keeps the hand-off workspace zeroed
+DGH_PAD8 = 0x200  # DL4SS_RNN_DGH_PAD8: each direction's bf16 dGh columns start 16-B aligned
+DEFER_BIAS = 0x400  # DL4SS_RNN_DEFER_BIAS: bias partials stay in the workspace (dl4ss_birnn_bias_reduce)
+
+
+def DOUT_SLABS(n):  # DL4SS_RNN_DOUT_SLABS(S): the BPTT sums dOut's S split-K slabs itself
+    return ((n - 1) & 3) << 12
+
+
+def birnn_fwd(cell, B, T, H, *, G, w_hh, b_hh, act, ws, ws_bytes, status, out=None, hprev=None, cs=None,
+              out_bf16=None, hprev_bf16=None, h_mean=None, precision="fp32", flags=0):
+    """One bidirectional layer's recurrence over the input projections G (dl4ss_birnn_fwd_mean, the
+    superset of dl4ss_birnn_fwd / _fwd_ex: absent tensors are None)."""
+    p = _lib.ptr
+    _lib.call("dl4ss_birnn_fwd_mean", CELLS[cell], PREC[precision] | flags, B, T, H, p(G), p(w_hh), p(b_hh), p(out),
+              p(hprev), p(act), p(cs), p(out_bf16), p(hprev_bf16), p(h_mean), p(ws), ws_bytes, p(status),
+              _lib.stream_ptr())
+
+
+def birnn_fwd_xw(cell, B, T, H, *, x, w_ih, b_ih, w_hh, b_hh, act, ws, ws_bytes, status, out=None, hprev=None,
+                 cs=None, out_bf16=None, hprev_bf16=None, h_mean=None, ws_zeroed=True):
+    """The recurrence with the input projection x w_ih^T + b_ih fused into it (dl4ss_birnn_fwd_xw_ex; bf16
+    rows x (B*T, Kin) and w_ih (2 NG H, Kin), row strides taken from the views)."""
+    p = _lib.ptr
+    _lib.call("dl4ss_birnn_fwd_xw_ex", CELLS[cell], B, T, H, p(x, True), x.shape[1], x.stride(0), p(w_ih, True),
+              w_ih.stride(0), p(b_ih), p(w_hh), p(b_hh), p(out), p(hprev), p(act), p(cs), p(out_bf16), p(hprev_bf16),
+              p(h_mean), p(ws), ws_bytes, p(status), _lib.stream_ptr(), int(ws_zeroed))
+
+
+def birnn_bwd(cell, B, T, H, *, w_hh, act, ws, ws_bytes, status, dOut=None, dOut_bcast=None, cs=None, hprev=None,
+              dG=None, dGh=None, dG_bf16=None, dGh_bf16=None, db_ih=None, db_hh=None, precision="fp32", flags=0):
+    """One bidirectional layer's BPTT (dl4ss_birnn_bwd_ex, the superset of dl4ss_birnn_bwd: absent
+    tensors are None)."""
+    p = _lib.ptr
+    _lib.call("dl4ss_birnn_bwd_ex", CELLS[cell], PREC[precision] | flags, B, T, H, p(dOut), p(dOut_bcast), p(w_hh),
+              p(act), p(cs), p(hprev), p(dG), p(dGh), p(dG_bf16), p(dGh_bf16), p(db_ih), p(db_hh), p(ws), ws_bytes,
+              p(status), _lib.stream_ptr())
+
+
+# split-precision operand images (dl4ss_f32_to_bf16_hilo), hi / lo per segment by pattern bit: three terms
+# [x_hi | x_lo | x_hi] . [w_hi | w_hi | w_lo] (K' = 3 K), two terms [x_hi | x_hi] . [w_hi | w_lo] (K' = 2 K)
+A_SPLIT, W_SPLIT = 0b010, 0b100
+A_SPLIT2, W_SPLIT2 = 0b00, 0b10
+
+
+def pad8(n):
+    """n rounded up to a multiple of 8 (16-B aligned bf16 operand rows)"""
+    return (n + 7) // 8 * 8
+
+
+def hilo(x, y, segw, pattern, nseg=3):
+    """y = the split image of the fp32 rows x: nseg segments of segw, hi / lo by pattern bits."""
+    _lib.call("dl4ss_f32_to_bf16_hilo", _lib.ptr(x, True), x.stride(0), x.shape[0], x.shape[1], _lib.ptr(y),
+              y.stride(0), segw, nseg, pattern, _lib.stream_ptr())
+
+
 def birnn_plan(cell, B, H, precision="bf16", max_wg=0):
     """The persistent recurrence's plan {BC, NG, J, nchunk, grid} under a co-residency budget
     of max_wg workgroups (0: the current device's); None when no plan fits (host-only for
@@ -371,7 +432,7 @@ def birnn_plan(cell, B, H, precision="bf16", max_wg=0):
     import ctypes
 
     info = (ctypes.c_int * 5)()
-    rc = _lib.lib().dl4ss_birnn_plan_info({"lstm": 0, "gru": 1}[cell], int(B), int(H),
+    rc = _lib.lib().dl4ss_birnn_plan_info(CELLS[cell], int(B), int(H),
                                           1 if precision == "bf16" else 0, int(max_wg), info)
     if rc != 0:
         return None

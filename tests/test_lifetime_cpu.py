@@ -84,3 +84,11 @@ def test_step_plan_flags(monkeypatch):
         monkeypatch.delenv(name)
     monkeypatch.setenv("DL4SS_WS_FILL", "1")
     assert engine.SepTrainer(net, 2, 2, 4000, mode="pit", precision="bf16")._ws_fill
+    monkeypatch.delenv("DL4SS_WS_FILL")
+    # a retired knob in the environment is refused by name, not silently ignored (whatever its value)
+    for name in ("DL4SS_DX_SPLIT", "DL4SS_DEFER_BIAS", "DL4SS_SIDE_LATE", "DL4SS_DW_SPLITS", "DL4SS_DW_CFG"):
+        monkeypatch.setenv(name, "1")
+        with pytest.raises(ValueError, match=name):
+            engine.SepTrainer(net, 2, 2, 4000, mode="pit", precision="bf16")
+        monkeypatch.delenv(name)
+    engine.SepTrainer(net, 2, 2, 4000, mode="pit", precision="bf16")

@@ -17,7 +17,7 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
-from dl4ss_amd import _lib, classifier, infer, ops, synth  # noqa: E402
+from dl4ss_amd import classifier, infer, ops, synth  # noqa: E402
 
 
 def timed(fn, reps, warmup):
@@ -62,21 +62,20 @@ def main():
                  mixtures_per_s=B / (r["median_ms"] * 1e-3), loss=float(tr.loss[0].item()))
         lines.append(r)
         # one forward and one BPTT launch of the middle layer on the step's own buffers
-        l, T, st = 1, tr.T, _lib.stream_ptr()
-        prec = ops.PREC[precision]
+        l, T = 1, tr.T
         G = tr.G.clone()
 
         def fwd():
-            _lib.call("dl4ss_birnn_fwd", 0, prec, B, T, H, _lib.ptr(G), _lib.ptr(cnet.cat_view("weight_hh", l)),
-                      _lib.ptr(cnet.cat_view("bias_hh", l)), _lib.ptr(tr.out[l]), _lib.ptr(tr.hprev[l]),
-                      _lib.ptr(tr.act[l]), _lib.ptr(tr.cs[l]), _lib.ptr(tr.rnn_ws), tr.ws_bytes, _lib.ptr(tr.status), st)
+            ops.birnn_fwd("lstm", B, T, H, G=G, w_hh=cnet.cat_view("weight_hh", l), b_hh=cnet.cat_view("bias_hh", l),
+                          out=tr.out[l], hprev=tr.hprev[l], act=tr.act[l], cs=tr.cs[l], ws=tr.rnn_ws,
+                          ws_bytes=tr.ws_bytes, status=tr.status, precision=precision)
 
         dH, dG = torch.randn(B * T, 2 * H, device=dev) * 1e-3, torch.empty_like(G)
 
         def bwd():
-            _lib.call("dl4ss_birnn_bwd_ex", 0, prec, B, T, H, _lib.ptr(dH), None, _lib.ptr(cnet.cat_view("weight_hh", l)),
-                      _lib.ptr(tr.act[l]), _lib.ptr(tr.cs[l]), _lib.ptr(tr.hprev[l]), _lib.ptr(dG), None, None, None,
-                      None, None, _lib.ptr(tr.rnn_ws), tr.ws_bytes, _lib.ptr(tr.status), st)
+            ops.birnn_bwd("lstm", B, T, H, dOut=dH, w_hh=cnet.cat_view("weight_hh", l), act=tr.act[l], cs=tr.cs[l],
+                          hprev=tr.hprev[l], dG=dG, ws=tr.rnn_ws, ws_bytes=tr.ws_bytes, status=tr.status,
+                          precision=precision)
 
         ops.gemm(tr.out[0].view(B * T, 2 * H), cnet.cat_view("weight_ih", l), transB=True,
                  bias=cnet.cat_view("bias_ih", l), out=G, precision=precision)

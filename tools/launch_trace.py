@@ -1,0 +1,183 @@
+"""The ordered list of C-ABI launches of two eager SepTrainer.step() calls, in a form two trees can compare.
+
+    python tools/launch_trace.py CASE out.json [--tree DIR]     record (DIR: the tree to import, default this one)
+    python tools/launch_trace.py --compare a.json b.json        print the first difference, or "identical"
+    python tools/launch_trace.py --list                         the case names
+
+``_lib.call`` is wrapped (record, then forward).  Integers and floats are recorded verbatim.  Every pointer --
+also each element of a ctypes pointer array, so the GroupedGemm tables and the conversion / bias-reduce lists --
+becomes (region, byte offset): a region is the torch storage that contains the address, numbered by first
+appearance in the trace; the storages are found after the steps by walking the trainer's and the net's
+attributes (tensors, lists, GroupedGemm objects) and the batch.  Stream handles are numbered the same way (the
+default stream is the null handle).  The short entry points (dl4ss_birnn_fwd, _fwd_ex, _fwd_xw, _bwd) are
+rewritten to their superset forms, padded with nulls where birnn.hip pads them, so that a tree that calls the
+short forms and one that calls the supersets compare equal.  Uses only _lib.call, engine.SepNet / SepTrainer and
+synth, so the same file runs against an older checkout (--tree)."""
+import bisect
+import ctypes
+import json
+import os
+import sys
+
+C2 = dict(B=32, N=32000, K=2, net=dict(cell="lstm", num_layers=4), tr=dict(mode="pit", precision="bf16"))
+GRU2 = dict(cell="gru", num_layers=2, adjust=False)
+
+
+def small(net, K=2, **tr):
+    return dict(B=4, N=8000, K=K, net=net, tr=tr)
+
+
+CASES = {
+    "c2": C2,
+    "gru2_k3_pit_bf16": small(GRU2, K=3, mode="pit", precision="bf16"),
+    "gru2_label_bf16s": small(GRU2, mode="label", precision="bf16s"),
+    "gru2_label_bf16s2": small(GRU2, mode="label", precision="bf16s2"),
+    "lstm2_label_fp32": small(dict(cell="lstm", num_layers=2), mode="label", precision="fp32"),
+    "gru2_crm_bf16": small(dict(cell="gru", num_layers=2, crm=True), mode="crm", precision="bf16"),
+    "gru2_crm_fp32": small(dict(cell="gru", num_layers=2, crm=True), mode="crm", precision="fp32"),
+    "lstm2_align_fp32": small(dict(cell="lstm", num_layers=2, attention="align"), mode="label", precision="fp32"),
+    "lstm6_bf16": small(dict(cell="lstm", num_layers=6), mode="pit", precision="bf16"),
+    "lstm2_bf16_rnn_fp32": small(dict(cell="lstm", num_layers=2), mode="pit", precision="bf16", rnn_precision="fp32"),
+    "c2_side0": dict(C2, env={"DL4SS_SIDE_DWLIN": "0"}),
+    "c2_slabs0": dict(C2, env={"DL4SS_DH_SLABS": "0"}),
+}
+
+# short entry point -> (superset, index at which birnn.hip inserts null pointers, how many)
+SUPERSET = {"dl4ss_birnn_fwd": ("dl4ss_birnn_fwd_mean", 12, 3), "dl4ss_birnn_fwd_ex": ("dl4ss_birnn_fwd_mean", 14, 1),
+            "dl4ss_birnn_fwd_xw": ("dl4ss_birnn_fwd_xw_ex", 18, 1), "dl4ss_birnn_bwd": ("dl4ss_birnn_bwd_ex", 13, 4)}
+
+
+def raw(a):
+    """One argument as recorded at call time: numbers verbatim, pointers tagged "p", arrays element-wise."""
+    if isinstance(a, ctypes.Array):
+        if a._type_ is ctypes.c_void_p:
+            return ["pa"] + [("p", v) for v in a]
+        return ["a"] + list(a)
+    if isinstance(a, ctypes.c_void_p):
+        return ("p", a.value)
+    if a is None:
+        return ("p", None)
+    assert isinstance(a, (int, float)), type(a)
+    return a
+
+
+def storages(roots):
+    """{base address: bytes} of every torch storage reachable from the roots through lists, tuples, dicts and
+    the attributes of the package's own objects (the trainer, the net, GroupedGemm)."""
+    import torch
+
+    found, seen, todo = {}, set(), list(roots)
+    while todo:
+        o = todo.pop()
+        if id(o) in seen:
+            continue
+        seen.add(id(o))
+        if isinstance(o, torch.Tensor):
+            s = o.untyped_storage()
+            found[s.data_ptr()] = max(found.get(s.data_ptr(), 0), s.nbytes())
+        elif isinstance(o, (list, tuple)):
+            todo += o
+        elif isinstance(o, dict):
+            todo += o.values()
+        elif type(o).__module__.startswith("dl4ss_amd") and hasattr(o, "__dict__"):
+            todo += vars(o).values()
+    return found
+
+
+def normalise(trace, regions, streams):
+    bases = sorted(regions)
+    rnum, snum, unknown = {}, {}, {}
+
+    def ptr(v):
+        if v is None:
+            return None
+        i = bisect.bisect_right(bases, v) - 1
+        if i >= 0 and v < bases[i] + max(regions[bases[i]], 1):
+            return ["r", rnum.setdefault(bases[i], len(rnum)), v - bases[i]]
+        if v in streams:
+            return ["s", snum.setdefault(v, len(snum))]
+        return ["?", unknown.setdefault(v, len(unknown))]
+
+    def arg(a):
+        if isinstance(a, tuple):
+            return ptr(a[1])
+        if isinstance(a, list):
+            return [arg(x) for x in a[1:]]
+        return a
+
+    out = []
+    for name, args in trace:
+        args = [arg(a) for a in args]
+        if name in SUPERSET:
+            name, at, n = SUPERSET[name]
+            args[at:at] = [None] * n
+        out.append([name, args])
+    return out, len(unknown)
+
+
+def record(case, out, tree):
+    sys.path.insert(0, tree)
+    cfg = CASES[case]
+    os.environ.update(cfg.get("env", {}))
+    import numpy as np
+    import torch
+
+    from dl4ss_amd import _lib, engine, ops, synth
+
+    dev = torch.device("cuda")
+    B, K, N = cfg["B"], cfg["K"], cfg["N"]
+    src, spk, u = synth.SyntheticMixtures(n_samples=N, k=K, seed=7).batch(B)
+    batch = (torch.from_numpy(src.astype(np.float32)).to(dev),
+             torch.from_numpy(synth.gains_for(u, K).astype(np.float32)).to(dev),
+             torch.from_numpy(spk.astype(np.int32)).to(dev))
+    net = engine.SepNet(device=dev, seed=11, **cfg["net"])
+    tr = engine.SepTrainer(net, B, K, N, **cfg["tr"])
+    trace, call = [], _lib.call
+
+    def recording_call(name, *args):
+        trace.append((name, [raw(a) for a in args]))
+        return call(name, *args)
+
+    _lib.call = recording_call
+    try:
+        losses = [float(tr.step(*batch)[0]) for _ in range(2)]
+    finally:
+        _lib.call = call
+    tr.check()
+    streams = {s.cuda_stream for s in (torch.cuda.current_stream(), getattr(tr, "_side_stream", None)) if s is not None}
+    calls, unknown = normalise(trace, storages([tr, net, batch, getattr(ops, "_gl_ws", {})]), streams)
+    with open(out, "w") as f:
+        json.dump(dict(case=case, losses=losses, unresolved_pointers=unknown, calls=calls), f)
+    print(f"{case}: {len(calls)} calls, {unknown} unresolved pointers, losses {losses}")
+
+
+def compare(a, b):
+    x, y = json.load(open(a)), json.load(open(b))
+    bad = [n for n, t in ((a, x), (b, y)) if t["unresolved_pointers"]]
+    if bad:
+        print(f"{x['case']}: unresolved pointers in {bad}: not comparable")
+        return False
+    for i, (p, q) in enumerate(zip(x["calls"], y["calls"])):
+        if p != q:
+            j = next((j for j, (s, t) in enumerate(zip(p[1], q[1])) if s != t), min(len(p[1]), len(q[1])))
+            where = "entry point" if p[0] != q[0] else f"argument {j}"
+            print(f"{x['case']}: call {i} differs ({where})\n  {a}: {p}\n  {b}: {q}")
+            return False
+    # (the first step's loss only: the fp32 step's split-K backward GEMMs add with float atomics, so its second
+    # loss varies in the last bits from run to run of one tree)
+    if len(x["calls"]) != len(y["calls"]) or x["losses"][:1] != y["losses"][:1]:
+        print(f"{x['case']}: {len(x['calls'])} vs {len(y['calls'])} calls, losses {x['losses']} vs {y['losses']}")
+        return False
+    print(f"{x['case']}: identical ({len(x['calls'])} calls)")
+    return True
+
+
+if __name__ == "__main__":
+    here = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    if sys.argv[1] == "--list":
+        print("\n".join(CASES))
+    elif sys.argv[1] == "--compare":
+        sys.exit(0 if compare(sys.argv[2], sys.argv[3]) else 1)
+    else:
+        tree = sys.argv[sys.argv.index("--tree") + 1] if "--tree" in sys.argv else here
+        record(sys.argv[1], sys.argv[2], os.path.abspath(tree))  # (--compare refuses a trace with unresolved pointers)
