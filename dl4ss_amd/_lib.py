@@ -101,6 +101,9 @@ SIGNATURES = {
     "dl4ss_disc_head_bwd": [I, P, P, P, P, F, I, I, I, P, P, P, P, P, P],
     "dl4ss_disc_conv64_bwd": [I, P, P, P, P, I, I, I, P, P, P, P, LL, P],
     "dl4ss_disc_conv1_bwd": [I, P, P, P, P, I, I, I, P, P, P, P, LL, P],
+    "dl4ss_mask_attn_loss_adv": [I, I, I, I, I, P, P, P, LL, P, LL, LL, P, F, F, P, P, P, LL, P, P, P, P, P],
+    "dl4ss_mask_attn_loss_adv_bf16v": [I, I, I, I, I, P, P, P, LL, P, LL, LL, P, F, F, P, P, P, LL, P, P, P, P, P],
+    "dl4ss_disc_adv_heads": [P, I, F, P, P, P, P],
 }
 # entry points that return a value rather than a hipError_t
 RESTYPES = {"dl4ss_birnn_workspace_bytes": ctypes.c_longlong, "dl4ss_colsum_bf16_part_bytes": ctypes.c_longlong,

@@ -495,6 +495,30 @@ __global__ void head_dz_kernel(const float* __restrict__ score, const float* __r
   if (loss) loss[0] = l * inv;
 }
 
+// The adversarial step's three loss heads (dis.py:622-624,642) over the scores [true (N); fake (N)]:
+// loss[0] = L_dt = mean (s_true - 1)^2, loss[1] = L_df = mean s_fake^2, loss[2] = L_adv = mean (s_fake - 1)^2
+// (unweighted), ds_dis (2N) = d(L_dt + L_df)/dscore = 2 (s - 1) / N | 2 s / N, ds_adv (N) =
+// lambda 2 (s_fake - 1) / N.  One thread, maps in order, the sums in fp64: N is the number of maps.
+__global__ void adv_heads_kernel(const float* __restrict__ score, int N, float lambda, float* __restrict__ loss,
+                                 float* __restrict__ ds_dis, float* __restrict__ ds_adv) {
+  if (threadIdx.x != 0 || blockIdx.x != 0) return;
+  const float inv = 1.0f / (float)N;
+  double lt = 0.0, lf = 0.0, la = 0.0;
+  for (int n = 0; n < N; ++n) {
+    const float st = score[n], sf = score[N + n];
+    const float et = st - 1.0f, ea = sf - 1.0f;
+    lt += (double)et * et;
+    lf += (double)sf * sf;
+    la += (double)ea * ea;
+    ds_dis[n] = 2.0f * et * inv;
+    ds_dis[N + n] = 2.0f * sf * inv;
+    ds_adv[n] = lambda * (2.0f * ea * inv);
+  }
+  loss[0] = (float)(lt / N);
+  loss[1] = (float)(lf / N);
+  loss[2] = (float)(la / N);
+}
+
 // dwf[c, h, w] = sum_n dz[n] y3[n, h, w, c] (maps in order), dy3[n, h, w, c] = dz[n] wf[c, h, w]
 template <typename T>
 __global__ __launch_bounds__(NT) void head_bwd_kernel(const T* __restrict__ y3, const float* __restrict__ wf,
@@ -666,6 +690,19 @@ DL4SS_API int dl4ss_disc_head_bwd(int prec, const void* y3, const float* wf, con
   else
     hipLaunchKernelGGL(head_bwd_kernel<bf16_t>, dim3(cdiv((long long)HW * CH, NT)), dim3(NT), 0, st,
                        (const bf16_t*)y3, wf, dz, N, HW, dwf, (bf16_t*)dy3);
+  DL4SS_CHECK_LAUNCH();
+  return 0;
+}
+
+// The adversarial step's loss heads: score (2 N) = [D(true maps); D(predicted maps)] -> loss (3) =
+// {L_dt, L_df, L_adv} (means over the N maps, L_adv unweighted), dscore_dis (2 N) for the backward of
+// L_dt + L_df over all maps, dscore_adv (N) = lambda dL_adv/dscore for the backward over the predicted maps
+// (both go to dl4ss_disc_head_bwd as its dscore).
+DL4SS_API int dl4ss_disc_adv_heads(const float* score, int N, float lambda, float* loss, float* dscore_dis,
+                                   float* dscore_adv, void* stream) {
+  DL4SS_REQUIRE(score && loss && dscore_dis && dscore_adv && N > 0);
+  hipLaunchKernelGGL(adv_heads_kernel, dim3(1), dim3(64), 0, as_stream(stream), score, N, lambda, loss, dscore_dis,
+                     dscore_adv);
   DL4SS_CHECK_LAUNCH();
   return 0;
 }

@@ -156,6 +156,43 @@ class SepNet(FlatParams):
             self.view(name).copy_(t)
 
 
+class DiscNet(FlatParams):
+    """Parameters of the adversarial Discriminator (TDAA_beta/main_run_sstune_dis.py:318-336) for (T, F)
+    maps, flat fp32 under the reference's eight ``state_dict`` keys with the shapes of
+    ``compat.myNet.Discriminator`` (a ``_dislayer_`` file or that module's state_dict loads unchanged;
+    ``checkpoint.load_reference_discriminator`` / ``save_reference_discriminator`` take a DiscNet as their
+    module), and the two flat gradients of the adversarial step: ``grad_dis`` = d(L_dt + L_df) and
+    ``grad_adv`` = d(lambda L_adv) (SepTrainer(adversary=...))."""
+
+    def __init__(self, T, F=129, device="cuda", seed=1):
+        hw = (ctypes.c_int * 6)()
+        feat = _lib.query("dl4ss_disc_dims", int(T), int(F), hw)
+        if feat < 0:
+            raise ValueError(f"DiscNet: a ({T}, {F}) map is smaller than the 15 x 15 minimum")
+        self.T, self.F, self.hw, self.feat = int(T), int(F), list(hw), feat
+        self._allocate([("cnn.weight", (64, 1, 3, 3)), ("cnn.bias", (64,)), ("cnn1.weight", (64, 64, 3, 3)),
+                        ("cnn1.bias", (64,)), ("cnn2.weight", (64, 64, 3, 3)), ("cnn2.bias", (64,)),
+                        ("final.weight", (1, feat)), ("final.bias", (1,))], device)
+        self.grad_dis = torch.zeros_like(self.flat)
+        self.grad_adv = torch.zeros_like(self.flat)
+        self.reset_parameters(seed)
+
+    def load_state_dict(self, sd):
+        """The eight keys, each with this net's shape (a file saved at another map size raises)."""
+        for name, shape in self.specs:
+            if tuple(sd[name].shape) != tuple(shape):
+                raise ValueError(f"DiscNet: {name} has shape {tuple(sd[name].shape)}, expected {tuple(shape)}")
+        super().load_state_dict(sd)
+
+    def reset_parameters(self, seed=1):
+        """torch's default initialisers of nn.Conv2d / nn.Linear: uniform +-1/sqrt(fan_in), weight and bias."""
+        g = torch.Generator().manual_seed(seed)
+        fan = {"cnn": 9, "cnn1": 576, "cnn2": 576, "final": self.feat}
+        for name, shape in self.specs:
+            k = 1.0 / math.sqrt(fan[name.split(".")[0]])
+            self.view(name).copy_(torch.empty(shape).uniform_(-k, k, generator=g))
+
+
 # settled A/B knobs (DESIGN.md section 11 keeps their last figures): the default of each is the only path now
 RETIRED_KNOBS = ("DL4SS_DX_SPLIT", "DL4SS_DEFER_BIAS", "DL4SS_SIDE_LATE", "DL4SS_DW_SPLITS", "DL4SS_DW_CFG")
 
@@ -247,12 +284,34 @@ class SepTrainer:
     """Buffers and the step schedule for one (B, K, N) workload."""
 
     def __init__(self, net, batch, k, n_samples, mode="label", precision="fp32", lr=2e-4, sum_weight=0.5,
-                 loss_channels=None, betas=(0.9, 0.999), eps=1e-8, process_group=None, rnn_precision=None):
+                 loss_channels=None, betas=(0.9, 0.999), eps=1e-8, process_group=None, rnn_precision=None,
+                 adversary=None, adv_weight=1.0, adv_lr=None, disc_adv_update=True):
         if mode not in ("label", "pit", "crm"):
             raise ValueError(mode)
         if (mode == "crm") != net.crm:
             raise ValueError("cRM mode needs a cRM net (query width 2E) and vice versa")
         self.align = getattr(net, "attention", "dot") == "align"
+        if adversary is not None:  # the adversarial step (_adv_setup): refused here, before any device call
+            T_ = ops.n_frames(n_samples)
+            if not isinstance(adversary, DiscNet):
+                raise ValueError("adversary: expected an engine.DiscNet")
+            if mode == "crm":
+                raise ValueError("adversary: the adversarial term is built for the magnitude modes, not 'crm'")
+            if loss_channels:
+                raise ValueError("adversary: loss_channels is unsupported with an adversary")
+            if self.align:
+                raise ValueError("adversary: attention='align' is unsupported with an adversary")
+            if process_group is not None:
+                raise ValueError("adversary: no data-parallel adversarial step (the Discriminator's gradients are "
+                                 "not all-reduced)")
+            if T_ < 15:
+                raise ValueError(f"adversary: {T_} frames, the Discriminator needs maps of at least 15 x 15")
+            if (adversary.T, adversary.F) != (T_, net.F):
+                raise ValueError(f"adversary: a DiscNet for ({adversary.T}, {adversary.F}) maps, this trainer's "
+                                 f"are ({T_}, {net.F})")
+            if (adversary.device.type, adversary.device.index or 0) != (net.device.type, net.device.index or 0):
+                raise ValueError("adversary: the DiscNet lives on another device than the net")
+        self.adversary = adversary
         if self.align:
             if mode == "crm":
                 raise ValueError("attention='align' supports the modes 'label' and 'pit', not 'crm'")
@@ -297,9 +356,11 @@ class SepTrainer:
             self.Xc_src = torch.empty(B, K, T, F, 2, **f32)
         else:
             self.Xc_mix = None
-            self._mag = torch.empty(B + B * K, T, F, **f32)
+            # (adversarial step: B K more maps behind the sources' for the predictions, so that one Discriminator
+            # forward runs over [true; predicted]; the STFT launch still covers the first B + B K only)
+            self._mag = torch.empty(B + B * K * (2 if adversary is not None else 1), T, F, **f32)
             self.mag_mix = self._mag[:B]
-            self.mag_src = self._mag[B:].view(B, K, T, F)
+            self.mag_src = self._mag[B:B + B * K].view(B, K, T, F)
         self.out = [torch.empty(B, T, 2 * H, **f32) for _ in range(net.L)]
         self.hprev = [torch.empty(B, T, 2 * H, **f32) for _ in range(net.L)]
         self.act = [torch.empty(B, T, 2, 4 * H, **f32) for _ in range(net.L)]
@@ -344,6 +405,8 @@ class SepTrainer:
         self._in_chain = False
         self._side_stream = self._side_gemm = self._fork_ev = None
         self._wb_ver = None
+        if adversary is not None:
+            self._adv_setup(adv_weight, adv_lr, disc_adv_update)
         if not self.fast:
             return
         # the bf16 step's operands, each produced directly as bf16 by the kernel that forms it (the BiRNN
@@ -557,9 +620,20 @@ class SepTrainer:
             return self.Xc_mix, TF, self.Xc_src, K * TF, TF
         return self.mag_mix, TF, self.mag_src, K * TF, TF
 
-    def attn(self, pass_, perm=None, mask_out=None, pred_out=None):
+    def attn(self, pass_, perm=None, mask_out=None, pred_out=None, gext=None):
+        """One pass of the fused attention + loss kernels.  ``gext`` (GRAD pass of an adversarial step): a
+        second gradient at the prediction, (B, K, T, F) -- the adversarial form of the same kernel."""
         X, xs, Y, ys, yks = self._attn_args()
         grad = pass_ == 1
+        if gext is not None:
+            bf16v = self.fast and not self.split
+            fn, v = ("dl4ss_mask_attn_loss_adv_bf16v", self.Vb) if bf16v else ("dl4ss_mask_attn_loss_adv", self.V)
+            _lib.call(fn, self.B, self.K, self.T, self.F, self.net.E, _lib.ptr(v), _lib.ptr(self.q), _lib.ptr(X), xs,
+                      _lib.ptr(Y), ys, yks, _lib.ptr(perm), self.s1, self.s2, _lib.ptr(gext),
+                      None if self.fast else _lib.ptr(self.V), _lib.ptr(self.dPreb) if self.fast else None,
+                      self.dPreb.stride(0) if self.fast else 0, _lib.ptr(self.part_loss), _lib.ptr(self.part_dq),
+                      _lib.ptr(mask_out), _lib.ptr(pred_out), _lib.stream_ptr())
+            return
         if self.align:
             net = self.net
             _lib.call("dl4ss_mask_attn_align_loss", pass_, self.B, self.K, self.T, self.F, net.E, _lib.ptr(self.V),
@@ -586,11 +660,15 @@ class SepTrainer:
         """Fused attention + loss + dPre (in place over V) + dq; returns loss (device)."""
         st = _lib.stream_ptr()
         perm = None
+        adv = self.adversary is not None
+        if self.mode == "pit" or adv:  # (an adversary in label order: a COST pass only for the predictions)
+            self.attn(0, pred_out=self.pred if adv else None)
         if self.mode == "pit":
-            self.attn(0)
             _lib.call("dl4ss_pit_select", _lib.ptr(self.part_loss), self.B, self.K, self.nblk, _lib.ptr(self.perm), st)
             perm = self.perm
-        self.attn(1, perm)
+        if adv:  # the Discriminator on [true; predicted], its two gradients and gext = d(lambda L_adv)/dpred
+            self._adv_disc()
+        self.attn(1, perm, gext=self.gext if adv else None)
         if self.align:
             # the loss from the same partials; dq and the three attention-weight gradients from the align
             # partials, straight into their views of the flat gradient (backward_early zeroes only the
@@ -606,6 +684,92 @@ class SepTrainer:
         _lib.call("dl4ss_loss_finalize", _lib.ptr(self.part_loss), self.B, self.K, self.nblk, _lib.ptr(perm),
                   self.s1, self.s2, _lib.ptr(self.loss), _lib.ptr(self.part_dq), self.net.W, _lib.ptr(self.dq), st)
         return self.loss
+
+    # ------------------------------------------------------------------ adversarial term
+    def _adv_setup(self, adv_weight, adv_lr, disc_adv_update):
+        """Buffers of the adversarial step (TDAA_beta/main_run_sstune_dis.py:613-647 with detach_fake, the
+        adversarial term weighted by ``adv_weight``): the Discriminator's activations over the 2 B K maps
+        [true; predicted], their gradients, the scores and loss heads, gext, the split-K workspace and the
+        Discriminator's Adam state.  It runs in fp32 for precision 'fp32', in the bf16 activation mode
+        otherwise."""
+        D, B, K, T, F = self.adversary, self.B, self.K, self.T, self.F
+        dev, N = self.net.device, self.B * self.K
+        self.adv_weight = float(adv_weight)
+        self.adv_lr = self.lr if adv_lr is None else adv_lr
+        self.disc_adv_update = bool(disc_adv_update)
+        self._dprec = ops.PREC["fp32" if self.precision == "fp32" else "bf16"]
+        dt = torch.float32 if self._dprec == 0 else torch.bfloat16
+        f32 = dict(device=dev, dtype=torch.float32)
+        self.pred = self._mag[B + N:].view(B, K, T, F)  # mask |X|, written by the COST pass (pred_out)
+        self._dmaps = self._mag[B:]  # (2 B K, T, F): the sources' magnitudes, then the predictions
+        self._dy = [torch.empty(2 * N, D.hw[2 * l], D.hw[2 * l + 1], 64, device=dev, dtype=dt) for l in range(3)]
+        self._ddy = [torch.empty_like(y) for y in self._dy]
+        self.adv_scores = torch.empty(2 * N, **f32)
+        self._dlogit = torch.empty(2 * N, **f32)
+        self._ddz = torch.empty(2 * N, **f32)
+        self._ds_dis = torch.empty(2 * N, **f32)
+        self._ds_adv = torch.empty(N, **f32)
+        self.adv_loss = torch.zeros(3, **f32)  # [L_dt, L_df, L_adv] (L_adv unweighted)
+        self.gext = torch.empty(B, K, T, F, **f32)
+        self._dws_bytes = _lib.query("dl4ss_disc_ws_bytes", 2 * N, T, F)
+        if self._dws_bytes < 0:
+            raise RuntimeError(f"Discriminator shape unsupported (N={2 * N}, T={T}, F={F})")
+        self._dws = torch.empty((self._dws_bytes + 3) // 4, **f32)
+        self.adv_m = torch.zeros_like(D.flat)
+        self.adv_v = torch.zeros_like(D.flat)
+        self.adv_step_count = 0
+
+    def _adv_disc(self):
+        """Scores of the 2 B K maps (one forward), the loss heads, then two backwards: all maps without the
+        input gradient -> grad_dis = d(L_dt + L_df), the predicted maps with conv1's dX -> grad_adv =
+        d(lambda L_adv) and gext = d(lambda L_adv)/dpred.  All on the current stream, at the pre-step weights."""
+        D, N, T, F, p, st = self.adversary, self.B * self.K, self.T, self.F, self._dprec, _lib.stream_ptr()
+        hw = D.hw
+        w = lambda name: _lib.ptr(D.view(name))  # noqa: E731
+        y1, y2, y3 = self._dy
+        _lib.call("dl4ss_disc_conv1_fwd", p, _lib.ptr(self._dmaps), w("cnn.weight"), w("cnn.bias"), 2 * N, T, F,
+                  _lib.ptr(y1), st)
+        _lib.call("dl4ss_disc_conv64_fwd", p, _lib.ptr(y1), w("cnn1.weight"), w("cnn1.bias"), 2 * N, hw[0], hw[1],
+                  _lib.ptr(y2), st)
+        _lib.call("dl4ss_disc_conv64_fwd", p, _lib.ptr(y2), w("cnn2.weight"), w("cnn2.bias"), 2 * N, hw[2], hw[3],
+                  _lib.ptr(y3), st)
+        _lib.call("dl4ss_disc_head_fwd", p, _lib.ptr(y3), w("final.weight"), w("final.bias"), 2 * N, hw[4], hw[5],
+                  _lib.ptr(self._dlogit), _lib.ptr(self.adv_scores), st)
+        _lib.call("dl4ss_disc_adv_heads", _lib.ptr(self.adv_scores), N, self.adv_weight, _lib.ptr(self.adv_loss),
+                  _lib.ptr(self._ds_dis), _lib.ptr(self._ds_adv), st)
+        self._adv_disc_bwd(0, 2 * N, self._ds_dis, D.grad_dis, None)
+        self._adv_disc_bwd(N, N, self._ds_adv, D.grad_adv, self.gext)
+
+    def _adv_disc_bwd(self, first, n, dscore, g, dx):
+        """The Discriminator's backward over the maps [first, first + n) from their dscore into the flat
+        gradient ``g``; ``dx`` (n, T, F): the input gradient too."""
+        D, T, F, p, st = self.adversary, self.T, self.F, self._dprec, _lib.stream_ptr()
+        hw = D.hw
+        w = lambda name: _lib.ptr(D.view(name))  # noqa: E731
+        gr = lambda name: _lib.ptr(D.view(name, g))  # noqa: E731
+        y1, y2, y3 = (y[first:first + n] for y in self._dy)
+        d1, d2, d3 = (d[:n] for d in self._ddy)
+        ws, wsn = _lib.ptr(self._dws), self._dws_bytes
+        _lib.call("dl4ss_disc_head_bwd", p, _lib.ptr(y3), w("final.weight"), _lib.ptr(self.adv_scores[first:first + n]),
+                  _lib.ptr(dscore), 0.0, n, hw[4], hw[5], None, _lib.ptr(self._ddz), gr("final.weight"),
+                  gr("final.bias"), _lib.ptr(d3), st)
+        _lib.call("dl4ss_disc_conv64_bwd", p, _lib.ptr(y2), _lib.ptr(y3), _lib.ptr(d3), w("cnn2.weight"), n, hw[2],
+                  hw[3], _lib.ptr(d2), gr("cnn2.weight"), gr("cnn2.bias"), ws, wsn, st)
+        _lib.call("dl4ss_disc_conv64_bwd", p, _lib.ptr(y1), _lib.ptr(y2), _lib.ptr(d2), w("cnn1.weight"), n, hw[0],
+                  hw[1], _lib.ptr(d1), gr("cnn1.weight"), gr("cnn1.bias"), ws, wsn, st)
+        _lib.call("dl4ss_disc_conv1_bwd", p, _lib.ptr(self._dmaps[first:first + n]), _lib.ptr(y1), _lib.ptr(d1),
+                  w("cnn.weight"), n, T, F, _lib.ptr(dx), gr("cnn.weight"), gr("cnn.bias"), ws, wsn, st)
+
+    def _adv_optimizer_step(self):
+        """The Discriminator's updates, in the reference's order (dis.py:627-628, 646-647: one optimizer over
+        both nets): Adam on grad_dis, then (disc_adv_update) Adam on grad_adv -- each a step of its own Adam
+        state, guarded by the same status word as the separation net's."""
+        D = self.adversary
+        for g in ((D.grad_dis, D.grad_adv) if self.disc_adv_update else (D.grad_dis,)):
+            self.adv_step_count += 1
+            _lib.call("dl4ss_adam_guarded", _lib.ptr(D.flat), _lib.ptr(g), _lib.ptr(self.adv_m), _lib.ptr(self.adv_v),
+                      D.numel, float(self.adv_lr), float(self.betas[0]), float(self.betas[1]), float(self.eps),
+                      self.adv_step_count, _lib.ptr(self.status), _lib.ptr(self.loss), _lib.stream_ptr())
 
     # ------------------------------------------------------------------ backward
     def _weight_grad_group(self):
@@ -951,6 +1115,8 @@ class SepTrainer:
         corrections follow the updates actually applied, as torch.optim.Adam's do.  Data
         parallel: the gradient is the SUM over ranks, scaled by 1 / world inside the update."""
         self.wait_allreduce()
+        if self.adversary is not None:  # the Discriminator's updates first (the reference's order)
+            self._adv_optimizer_step()
         self.step_count += 1
         shadow = self._shadow if (self._shadow_on and hasattr(self, "_shadow")) else None
         ops.adam_(self.net.flat, self.net.grad, self.m, self.v, self.step_count, self.lr, self.betas, self.eps,
@@ -1085,5 +1251,7 @@ class SepTrainer:
             self.status.zero_()
             self.rnn_ws_all.zero_()  # a timed-out launch's half-written hand-offs must not reach the next
             self.step_count -= refused
+            if self.adversary is not None:  # a refused step refused the Discriminator's updates too
+                self.adv_step_count -= refused * (2 if self.disc_adv_update else 1)
             where = "on this rank" if s else "on a data-parallel peer"
             raise RuntimeError(f"BiRNN hand-off timed out {where} (status {s}): {refused} update(s) refused")

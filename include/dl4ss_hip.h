@@ -329,6 +329,23 @@ int dl4ss_mask_attn_loss_bf16v(int pass, int crm, int B, int K, int T, int F, in
                                long long y_kstride, const int* perm, float s1, float s2, float* dPre, void* dPre_bf16,
                                long long dpre_bf16_ld, float* part_loss, float* part_dq, float* mask_out,
                                float* pred_out, void* stream);
+/* The magnitude path's GRAD pass (pass 1, crm 0 of dl4ss_mask_attn_loss_ex) with a second gradient at the
+ * prediction pred = mask |X|: dpred_extra (B, K, T*F) fp32 in pred_out's layout, e.g. the Discriminator's
+ * input gradient on the predicted maps (the adversarial step: dis.py:642-646, loss_multi_speech + the
+ * "fake looks real" term).  dm = (2 s1 (m x - y) + dpred_extra) x + 2 s2 ds; the loss partials are those of
+ * the call without it, bit for bit.  K = 1..3, E = 50.  The kernel form follows dPre_bf16 as in _ex. */
+int dl4ss_mask_attn_loss_adv(int B, int K, int T, int F, int E, const float* V, const float* q, const float* X,
+                             long long x_bstride, const float* Y, long long y_bstride, long long y_kstride,
+                             const int* perm, float s1, float s2, const float* dpred_extra, float* dPre,
+                             void* dPre_bf16, long long dpre_bf16_ld, float* part_loss, float* part_dq,
+                             float* mask_out, float* pred_out, void* stream);
+/* dl4ss_mask_attn_loss_adv with V in bf16 (as dl4ss_mask_attn_loss_bf16v). */
+int dl4ss_mask_attn_loss_adv_bf16v(int B, int K, int T, int F, int E, const void* V_bf16, const float* q,
+                                   const float* X, long long x_bstride, const float* Y, long long y_bstride,
+                                   long long y_kstride, const int* perm, float s1, float s2,
+                                   const float* dpred_extra, float* dPre, void* dPre_bf16, long long dpre_bf16_ld,
+                                   float* part_loss, float* part_dq, float* mask_out, float* pred_out,
+                                   void* stream);
 /* PIT: per utterance the lowest-index permutation minimising the summed costs. */
 int dl4ss_pit_select(const float* part_loss, int B, int K, int nblk, int* perm, void* stream);
 /* loss_out[3] = {total, MSE term, weighted sum-to-one term}; dq = sum of partials. */
@@ -513,6 +530,12 @@ int dl4ss_disc_head_fwd(int prec, const void* y3, const float* wf, const float* 
 int dl4ss_disc_head_bwd(int prec, const void* y3, const float* wf, const float* score, const float* dscore,
                         float target, int N, int H3, int W3, float* loss, float* dz, float* dwf, float* dbf, void* dy3,
                         void* stream);
+/* The adversarial step's loss heads (dis.py:622-624,642): score (2 N) = [D(true maps); D(predicted maps)] ->
+ * loss (3) = {mean (s_true - 1)^2, mean s_fake^2, mean (s_fake - 1)^2}, dscore_dis (2 N) = the gradient of
+ * the first two at every score, dscore_adv (N) = lambda times the third's at the predicted maps' scores;
+ * both feed dl4ss_disc_head_bwd's dscore.  Fixed summation order. */
+int dl4ss_disc_adv_heads(const float* score, int N, float lambda, float* loss, float* dscore_dis, float* dscore_adv,
+                         void* stream);
 /* 64 -> 64 layer backward from dy and the saved post-ReLU y (gate y > 0 applied on load): dw (64, 64, 3, 3),
  * db (64) and, when dx is not NULL, dx (N, Hin, Win, 64) with every element written (exact zeros where no
  * window reaches).  ws / ws_bytes: dl4ss_disc_ws_bytes of the network this layer belongs to. */
