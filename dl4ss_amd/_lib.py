@@ -80,6 +80,9 @@ SIGNATURES = {
     "dl4ss_adam_guarded_dp": [P, P, P, P, LL, F, F, F, F, I, P, P, P, P],
     "dl4ss_adam_guarded_dp_scaled": [P, P, P, P, LL, F, F, F, F, I, P, P, F, P, P],
     "dl4ss_adam_guarded_dp_scaled_bf16": [P, P, P, P, LL, F, F, F, F, I, P, P, F, P, I, P, P, P, P, P, P],
+    "dl4ss_grad_sumsq_parts": [LL],
+    "dl4ss_grad_sumsq": [P, LL, P, P],
+    "dl4ss_adam_clipped": [P, P, P, P, LL, F, F, F, F, I, P, P, F, P, I, P, P, P, P, P, P, I, F, P, P, P],
     "dl4ss_status_flag": [P, P, P],
     "dl4ss_birnn_plan_info": [I, I, I, I, I, P],
     "dl4ss_debug_set_spin_limit": [ctypes.c_uint],
@@ -107,7 +110,7 @@ SIGNATURES = {
 }
 # entry points that return a value rather than a hipError_t
 RESTYPES = {"dl4ss_birnn_workspace_bytes": ctypes.c_longlong, "dl4ss_colsum_bf16_part_bytes": ctypes.c_longlong,
-            "dl4ss_gemm_bf16_gl_ws_bytes": ctypes.c_longlong,
+            "dl4ss_gemm_bf16_gl_ws_bytes": ctypes.c_longlong, "dl4ss_grad_sumsq_parts": ctypes.c_longlong,
             "dl4ss_gemm_bf16_gl_grouped_ws_bytes": ctypes.c_longlong, "dl4ss_attn_nblk": ctypes.c_int,
             "dl4ss_attn_dot_nblk": ctypes.c_int, "dl4ss_attn_align_nblk": ctypes.c_int,
             "dl4ss_attn_align_part_floats": ctypes.c_longlong, "dl4ss_disc_ws_bytes": ctypes.c_longlong,

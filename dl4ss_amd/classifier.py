@@ -24,11 +24,17 @@ class ClassifierTrainer:
     """``precision``: "fp32" -- fp32 GEMMs, exact fp32 recurrence (precision 0); "bf16" -- bf16 GEMM
     operands, bf16 MFMA recurrent matvec (precision 1), fp32 accumulate and state everywhere.
     ``lr``: what the reference's optimizer is built with (1e-5, ``:395``); ``schedule.classifier()`` halves
-    it from epoch 0 on."""
+    it from epoch 0 on.
+    ``clip_norm``: clip the gradient's global L2 norm to it on device (torch.nn.utils.clip_grad_norm_'s
+    arithmetic; +inf: measure and guard only), and refuse an update whose gradient holds an Inf or NaN;
+    ``grad_norm`` (device float[2], valid after optimizer_step(), not synced) then holds the norm before
+    clipping and the coefficient.  None: no extra launch, the unclipped step."""
 
-    def __init__(self, cnet, batch, k, n_samples, precision="fp32", lr=1e-5, betas=(0.9, 0.999), eps=1e-8):
+    def __init__(self, cnet, batch, k, n_samples, precision="fp32", lr=1e-5, betas=(0.9, 0.999), eps=1e-8,
+                 clip_norm=None):
         if precision not in ops.PREC:
             raise ValueError(f"precision {precision!r}: expected one of {sorted(ops.PREC)}")
+        self.clip_norm = None if clip_norm is None else ops.check_clip_norm(clip_norm)
         self.net, self.B, self.K, self.N = cnet, batch, k, n_samples
         self.precision = precision
         self.lr, self.betas, self.eps = lr, betas, eps
@@ -68,6 +74,11 @@ class ClassifierTrainer:
         self.m = torch.zeros_like(cnet.flat)
         self.v = torch.zeros_like(cnet.flat)
         self.step_count = 0
+        self.skipped_nonfinite = 0  # updates refused for a non-finite gradient (counted by check())
+        if self.clip_norm is not None:
+            self._clip_part = torch.zeros(ops.grad_sumsq_parts(cnet.flat.numel()), device=dev, dtype=torch.float64)
+            self.grad_norm = torch.zeros(2, **f32)
+            self._nonfinite = torch.zeros(1, device=dev, dtype=torch.int32)
 
     # ------------------------------------------------------------------ features
     def features(self, raw=None, gains=None, feats=None):
@@ -143,10 +154,15 @@ class ClassifierTrainer:
     # ------------------------------------------------------------------ Adam
     def optimizer_step(self):
         """Adam on the flat buffers; refused on device (parameters untouched, loss[0] = NaN, status[1]
-        counts it) when a recurrence hand-off of this step timed out."""
+        counts it) when a recurrence hand-off of this step timed out.  With clip_norm: one sum-of-squares
+        launch first, then the clipped Adam, which also refuses a gradient that holds an Inf or NaN."""
         self.step_count += 1
+        clip = None
+        if self.clip_norm is not None:
+            ops.grad_sumsq(self.net.grad, self._clip_part)
+            clip = (self._clip_part, self.clip_norm, self.grad_norm, self._nonfinite)
         ops.adam_(self.net.flat, self.net.grad, self.m, self.v, self.step_count, self.lr, self.betas, self.eps,
-                  status=self.status, loss=self.loss)
+                  status=self.status, loss=self.loss, clip=clip)
 
     def step(self, raw=None, gains=None, y_map=None, feats=None):
         """One training step on device-resident inputs; returns the loss tensor (not synced)."""
@@ -160,11 +176,19 @@ class ClassifierTrainer:
     def check(self):
         """Raise if a recurrence hand-off timed out since the last check (the guarded Adam already
         refused every update from then on); the refused steps leave step_count, the status word and the
-        hand-off workspace are reset, so training can continue."""
+        hand-off workspace are reset, so training can continue.  Updates refused only because the gradient
+        held an Inf or NaN (clip_norm) leave step_count too, are added to skipped_nonfinite, and do not
+        raise.  Until this runs, the bias corrections of later steps count a refused step, time-out or
+        non-finite alike."""
         torch.cuda.synchronize()
         s, refused = (int(x) for x in self.status.tolist())
+        nonfinite = int(self._nonfinite.item()) if self.clip_norm is not None else 0
         if s or refused:
             self.status.zero_()
-            self.rnn_ws.zero_()
             self.step_count -= refused
-            raise RuntimeError(f"BiRNN hand-off timed out (status {s}): {refused} update(s) refused")
+            if nonfinite:
+                self._nonfinite.zero_()
+                self.skipped_nonfinite += nonfinite
+            if s or refused > nonfinite:
+                self.rnn_ws.zero_()
+                raise RuntimeError(f"BiRNN hand-off timed out (status {s}): {refused - nonfinite} update(s) refused")

@@ -1,5 +1,6 @@
 // Small fused kernels of the separation step: speaker queries (embedding gather +
-// ADDJUST), their backward, bias column sums and the Adam update.
+// ADDJUST), their backward, bias column sums, the gradient's sum of squares (global-norm clip) and the Adam
+// update.
 #include "common.h"
 
 namespace {
@@ -340,16 +341,72 @@ __device__ __forceinline__ void shadow_store4(const ShadowSegs& sh, long long i,
   shadow_store(sh, i, x.x); shadow_store(sh, i + 1, x.y); shadow_store(sh, i + 2, x.z); shadow_store(sh, i + 3, x.w);
 }
 
+// Sum of squares of the flat gradient for the global-norm clip: part[j] = the fp64 sum of g[i]^2 over the
+// j-th contiguous range of `per` quads (the n % 4 tail goes to the last range).  The ranges and the order of
+// every addition depend on n alone (sumsq_parts), so the same gradient gives the same bits on any device
+// partition and on every run: no atomics, one store per workgroup.  Each element is widened to fp64 (its
+// square is then exact) and accumulated in fp64; the loop issues four 16-B loads per thread before it adds.
+constexpr int SUMSQ_MAX_PARTS = 1024;
+constexpr int SUMSQ_THREADS = 256;
+constexpr long long SUMSQ_MIN_RANGE = 4096;  // floats per range before a second range is opened
+static inline long long sumsq_parts(long long n) {
+  const long long p = (n + SUMSQ_MIN_RANGE - 1) / SUMSQ_MIN_RANGE;
+  return p < 1 ? 1 : (p > SUMSQ_MAX_PARTS ? SUMSQ_MAX_PARTS : p);
+}
+__device__ __forceinline__ double sq4(float4 x, double acc) {
+  const double a = (double)x.x, b = (double)x.y, c = (double)x.z, d = (double)x.w;
+  return fma(d, d, fma(c, c, fma(b, b, fma(a, a, acc))));
+}
+// every thread of a 256-thread block gets the sum of the block's values (a fixed tree: butterfly inside
+// each wave, then the four wave sums in wave order)
+__device__ __forceinline__ double block_sum_d(double v, double* sd) {
+  v = wave_sum_d(v);
+  if ((threadIdx.x & 63) == 0) sd[threadIdx.x >> 6] = v;
+  __syncthreads();
+  return ((sd[0] + sd[1]) + sd[2]) + sd[3];
+}
+__global__ __launch_bounds__(SUMSQ_THREADS) void grad_sumsq_kernel(const float* __restrict__ g, long long n,
+                                                                   long long per, double* __restrict__ part) {
+  __shared__ double sd[SUMSQ_THREADS / 64];
+  const long long nq = n >> 2;
+  const long long q0 = min(nq, (long long)blockIdx.x * per), q1 = min(nq, q0 + per);
+  const float4* g4 = reinterpret_cast<const float4*>(g);
+  double a0 = 0.0, a1 = 0.0;
+  long long q = q0 + threadIdx.x;
+  for (; q + 3 * SUMSQ_THREADS < q1; q += 4 * SUMSQ_THREADS) {
+    const float4 x0 = g4[q], x1 = g4[q + SUMSQ_THREADS], x2 = g4[q + 2 * SUMSQ_THREADS],
+                 x3 = g4[q + 3 * SUMSQ_THREADS];
+    a0 = sq4(x0, a0); a1 = sq4(x1, a1); a0 = sq4(x2, a0); a1 = sq4(x3, a1);
+  }
+  for (; q < q1; q += SUMSQ_THREADS) a0 = sq4(g4[q], a0);
+  if (blockIdx.x == gridDim.x - 1 && threadIdx.x == 0)  // the n % 4 tail
+    for (long long i = nq << 2; i < n; ++i) a1 = fma((double)g[i], (double)g[i], a1);
+  const double s = block_sum_d(a0 + a1, sd);
+  if (threadIdx.x == 0) part[blockIdx.x] = s;
+}
+
+// the clipped update's extra arguments (adam_kernel<SH, true>)
+struct ClipArgs {
+  const double* part;  // grad_sumsq_kernel's partials
+  int n_part;
+  float max_norm;
+  float* gnorm;        // [2]: the norm of the mean gradient before clipping, the coefficient c (may be NULL)
+  int* nonfinite;      // [1]: updates refused for a non-finite gradient
+};
+
 // torch.optim.Adam (weight_decay 0, amsgrad off; m via lerp as torch) on flat fp32 buffers
 // (EvalVer.py:538-544,673-675: Adam(lr=2e-4), betas (0.9, 0.999), eps 1e-8).  SH: also the bf16
-// shadow copies of the updated parameters (bitwise dl4ss_f32_to_bf16_2d_multi of the new values)
-template <bool SH>
+// shadow copies of the updated parameters (bitwise dl4ss_f32_to_bf16_2d_multi of the new values).
+// CLIP: the global-norm clip of torch.nn.utils.clip_grad_norm_ on the mean gradient, folded into gscale.
+// Every block sums the partials in the same fixed order (<= 8 KB from L2) and so forms the same factor, or
+// takes the same refusal when the sum is not finite; without CLIP the code is the unclipped kernel's.
+template <bool SH, bool CLIP>
 __global__ __launch_bounds__(256) void adam_kernel(float* __restrict__ p, const float* __restrict__ g,
                                                    float* __restrict__ m, float* __restrict__ v, long long n,
                                                    float lr, float b1, float b2, float eps, float bc1, float bc2s,
                                                    const int* __restrict__ status, int* __restrict__ refused,
                                                    const float* __restrict__ dp_flag, float gscale,
-                                                   float* __restrict__ loss, ShadowSegs sh) {
+                                                   float* __restrict__ loss, ShadowSegs sh, ClipArgs cl) {
   // refuse the update when a recurrence hand-off of this step timed out on this rank
   // (status[0]) or on any data-parallel peer (dp_flag: the all-reduced status flag)
   if ((status && status[0]) || (dp_flag && dp_flag[0] != 0.f)) {
@@ -358,6 +415,26 @@ __global__ __launch_bounds__(256) void adam_kernel(float* __restrict__ p, const 
       if (refused) refused[0] += 1;  // refused-update count: the host rolls its step count back by it
     }
     return;
+  }
+  if constexpr (CLIP) {
+    __shared__ double sd[4];
+    double s = 0.0;
+    for (int j = threadIdx.x; j < cl.n_part; j += 256) s += cl.part[j];
+    s = block_sum_d(s, sd);
+    // fp64 throughout: nrm = ||g * gscale||, c = min(1, max_norm / (nrm + 1e-6)), one fp32 factor f = gscale c
+    const double nrm = (double)gscale * sqrt(s);
+    const double c = fmin(1.0, (double)cl.max_norm / (nrm + 1e-6));
+    if (!isfinite(s)) {  // an Inf or NaN in the gradient: refused as a timed-out step is, and counted
+      if (blockIdx.x == 0 && threadIdx.x == 0) {
+        if (loss) loss[0] = __builtin_nanf("");
+        if (refused) refused[0] += 1;
+        cl.nonfinite[0] += 1;
+        if (cl.gnorm) { cl.gnorm[0] = (float)nrm; cl.gnorm[1] = 0.f; }
+      }
+      return;
+    }
+    if (blockIdx.x == 0 && threadIdx.x == 0 && cl.gnorm) { cl.gnorm[0] = (float)nrm; cl.gnorm[1] = (float)c; }
+    gscale = (float)((double)gscale * c);  // c == 1: bitwise gscale
   }
   const float step = lr / bc1;
   for (long long i = (blockIdx.x * (long long)blockDim.x + threadIdx.x) * 4; i < n;
@@ -464,19 +541,24 @@ DL4SS_API int dl4ss_colsum(const float* A, long long lda, int M, int N, float* o
 namespace {
 int adam_launch(float* p, const float* g, float* m, float* v, long long n, float lr, float beta1, float beta2,
                 float eps, int step, const int* status, int* refused, const float* dp_flag, float gscale,
-                float* loss, void* stream, const ShadowSegs* sh = nullptr) {
+                float* loss, void* stream, const ShadowSegs* sh = nullptr, const ClipArgs* cl = nullptr) {
   DL4SS_REQUIRE(p && g && m && v && n >= 0 && step >= 1);
   if (n == 0) return 0;
   // bias corrections in double on the host, as torch computes them in Python floats
   const float bc1 = (float)(1.0 - pow((double)beta1, (double)step));
   const float bc2s = (float)sqrt(1.0 - pow((double)beta2, (double)step));
   const unsigned grid = (unsigned)min(8192LL, (n / 4 + 255) / 256 + 1);
-  if (sh && sh->n > 0)
-    hipLaunchKernelGGL(adam_kernel<true>, dim3(grid), dim3(256), 0, as_stream(stream), p, g, m, v, n, lr, beta1, beta2,
-                       eps, bc1, bc2s, status, refused, dp_flag, gscale, loss, *sh);
-  else
-    hipLaunchKernelGGL(adam_kernel<false>, dim3(grid), dim3(256), 0, as_stream(stream), p, g, m, v, n, lr, beta1,
-                       beta2, eps, bc1, bc2s, status, refused, dp_flag, gscale, loss, ShadowSegs{});
+  const bool shadows = sh && sh->n > 0;
+#define ADAM_LAUNCH(SH_, CLIP_)                                                                                      \
+  hipLaunchKernelGGL((adam_kernel<SH_, CLIP_>), dim3(grid), dim3(256), 0, as_stream(stream), p, g, m, v, n, lr, beta1, \
+                     beta2, eps, bc1, bc2s, status, refused, dp_flag, gscale, loss, shadows ? *sh : ShadowSegs{},      \
+                     cl ? *cl : ClipArgs{})
+  if (cl) {
+    if (shadows) ADAM_LAUNCH(true, true); else ADAM_LAUNCH(false, true);
+  } else {
+    if (shadows) ADAM_LAUNCH(true, false); else ADAM_LAUNCH(false, false);
+  }
+#undef ADAM_LAUNCH
   DL4SS_CHECK_LAUNCH();
   return 0;
 }
@@ -520,18 +602,11 @@ DL4SS_API int dl4ss_status_flag(const int* status, float* flag, void* stream) {
   return 0;
 }
 
-// dl4ss_adam_guarded_dp_scaled that also writes bf16 shadow copies of the updated parameters: segment
-// s (s < nseg <= 8) maps the flat range [seg_off, seg_off + rows*cols) row-major onto seg_y (row stride
-// seg_ldy >= cols bf16; columns >= cols are not written).  The step's bf16 weight operands then need
-// no conversion pass before the next forward (bitwise dl4ss_f32_to_bf16_2d_multi of the new values;
-// a refused update leaves parameters and shadows untouched).
-DL4SS_API int dl4ss_adam_guarded_dp_scaled_bf16(float* p, const float* g, float* m, float* v, long long n, float lr,
-                                                float beta1, float beta2, float eps, int step, int* status,
-                                                const float* dp_flag, float gscale, float* loss, int nseg,
-                                                const long long* seg_off, const int* seg_rows, const int* seg_cols,
-                                                void* const* seg_y, const long long* seg_ldy, void* stream) {
+namespace {
+// the shadow-segment arrays of the entry points below, checked and packed for the kernel
+int shadow_segs(ShadowSegs& sh, long long n, int nseg, const long long* seg_off, const int* seg_rows,
+                const int* seg_cols, void* const* seg_y, const long long* seg_ldy) {
   DL4SS_REQUIRE(nseg >= 0 && nseg <= SHADOW_MAX && (nseg == 0 || (seg_off && seg_rows && seg_cols && seg_y && seg_ldy)));
-  ShadowSegs sh{};
   sh.n = nseg;
   for (int i = 0; i < nseg; ++i) {
     DL4SS_REQUIRE(seg_y[i] && seg_rows[i] >= 0 && seg_cols[i] > 0 && seg_ldy[i] >= seg_cols[i] && seg_off[i] >= 0 &&
@@ -543,6 +618,55 @@ DL4SS_API int dl4ss_adam_guarded_dp_scaled_bf16(float* p, const float* g, float*
     sh.ldy[i] = seg_ldy[i];
     sh.y[i] = reinterpret_cast<unsigned short*>(seg_y[i]);
   }
+  return 0;
+}
+}  // namespace
+
+// dl4ss_adam_guarded_dp_scaled that also writes bf16 shadow copies of the updated parameters: segment
+// s (s < nseg <= 8) maps the flat range [seg_off, seg_off + rows*cols) row-major onto seg_y (row stride
+// seg_ldy >= cols bf16; columns >= cols are not written).  The step's bf16 weight operands then need
+// no conversion pass before the next forward (bitwise dl4ss_f32_to_bf16_2d_multi of the new values;
+// a refused update leaves parameters and shadows untouched).
+DL4SS_API int dl4ss_adam_guarded_dp_scaled_bf16(float* p, const float* g, float* m, float* v, long long n, float lr,
+                                                float beta1, float beta2, float eps, int step, int* status,
+                                                const float* dp_flag, float gscale, float* loss, int nseg,
+                                                const long long* seg_off, const int* seg_rows, const int* seg_cols,
+                                                void* const* seg_y, const long long* seg_ldy, void* stream) {
+  ShadowSegs sh{};
+  if (int rc = shadow_segs(sh, n, nseg, seg_off, seg_rows, seg_cols, seg_y, seg_ldy)) return rc;
   return adam_launch(p, g, m, v, n, lr, beta1, beta2, eps, step, status, status ? status + 1 : nullptr, dp_flag, gscale,
                      loss, stream, &sh);
+}
+
+// ---- global-norm gradient clipping ----
+DL4SS_API long long dl4ss_grad_sumsq_parts(long long n) { return sumsq_parts(n); }
+
+// part[0 .. dl4ss_grad_sumsq_parts(n)): fp64 sums of squares of fixed contiguous ranges of g
+DL4SS_API int dl4ss_grad_sumsq(const float* g, long long n, double* part, void* stream) {
+  DL4SS_REQUIRE(g && part && n >= 0 && ((uintptr_t)g & 15) == 0 && ((uintptr_t)part & 7) == 0);
+  const long long parts = sumsq_parts(n);
+  const long long per = ((n >> 2) + parts - 1) / parts;  // quads per range
+  hipLaunchKernelGGL(grad_sumsq_kernel, dim3((unsigned)parts), dim3(SUMSQ_THREADS), 0, as_stream(stream), g, n, per,
+                     part);
+  DL4SS_CHECK_LAUNCH();
+  return 0;
+}
+
+// dl4ss_adam_guarded_dp_scaled_bf16 with the gradient's global norm clipped to max_norm (part NULL: that
+// entry itself).  A non-finite sum refuses the update and counts it in nonfinite[0] besides status[1].
+DL4SS_API int dl4ss_adam_clipped(float* p, const float* g, float* m, float* v, long long n, float lr, float beta1,
+                                 float beta2, float eps, int step, int* status, const float* dp_flag, float gscale,
+                                 float* loss, int nseg, const long long* seg_off, const int* seg_rows,
+                                 const int* seg_cols, void* const* seg_y, const long long* seg_ldy,
+                                 const double* part, int n_part, float max_norm, float* gnorm, int* nonfinite,
+                                 void* stream) {
+  ShadowSegs sh{};
+  if (int rc = shadow_segs(sh, n, nseg, seg_off, seg_rows, seg_cols, seg_y, seg_ldy)) return rc;
+  if (!part)
+    return adam_launch(p, g, m, v, n, lr, beta1, beta2, eps, step, status, status ? status + 1 : nullptr, dp_flag,
+                       gscale, loss, stream, &sh);
+  DL4SS_REQUIRE(n_part == sumsq_parts(n) && max_norm > 0.f && nonfinite && ((uintptr_t)part & 7) == 0);
+  const ClipArgs cl{part, n_part, max_norm, gnorm, nonfinite};
+  return adam_launch(p, g, m, v, n, lr, beta1, beta2, eps, step, status, status ? status + 1 : nullptr, dp_flag, gscale,
+                     loss, stream, &sh, &cl);
 }

@@ -281,13 +281,25 @@ def step_plan(net, batch, n_samples, precision, rnn_precision=None, process_grou
 
 
 class SepTrainer:
-    """Buffers and the step schedule for one (B, K, N) workload."""
+    """Buffers and the step schedule for one (B, K, N) workload.
+
+    ``clip_norm``: clip the global L2 norm of the global-batch mean gradient to it inside optimizer_step()
+    (torch.nn.utils.clip_grad_norm_'s arithmetic, on device; +inf measures and guards only) and refuse an update
+    whose gradient holds an Inf or NaN; ``grad_norm`` (device float[2]) then holds the norm before clipping and the
+    coefficient, ``skipped_nonfinite`` what check() has counted.  ``adv_clip_norm``: the same for each of the
+    Discriminator's updates (``adv_grad_norm``, float[2, 2]).  None (the default): no launch is added."""
 
     def __init__(self, net, batch, k, n_samples, mode="label", precision="fp32", lr=2e-4, sum_weight=0.5,
                  loss_channels=None, betas=(0.9, 0.999), eps=1e-8, process_group=None, rnn_precision=None,
-                 adversary=None, adv_weight=1.0, adv_lr=None, disc_adv_update=True):
+                 adversary=None, adv_weight=1.0, adv_lr=None, disc_adv_update=True, clip_norm=None,
+                 adv_clip_norm=None):
         if mode not in ("label", "pit", "crm"):
             raise ValueError(mode)
+        # gradient clipping (_clip_setup): thresholds checked here, before any device call
+        self.clip_norm = None if clip_norm is None else ops.check_clip_norm(clip_norm)
+        self.adv_clip_norm = None if adv_clip_norm is None else ops.check_clip_norm(adv_clip_norm, "adv_clip_norm")
+        if adv_clip_norm is not None and adversary is None:
+            raise ValueError("adv_clip_norm needs an adversary")
         if (mode == "crm") != net.crm:
             raise ValueError("cRM mode needs a cRM net (query width 2E) and vice versa")
         self.align = getattr(net, "attention", "dot") == "align"
@@ -407,6 +419,7 @@ class SepTrainer:
         self._wb_ver = None
         if adversary is not None:
             self._adv_setup(adv_weight, adv_lr, disc_adv_update)
+        self._clip_setup()
         if not self.fast:
             return
         # the bf16 step's operands, each produced directly as bf16 by the kernel that forms it (the BiRNN
@@ -760,13 +773,37 @@ class SepTrainer:
         _lib.call("dl4ss_disc_conv1_bwd", p, _lib.ptr(self._dmaps[first:first + n]), _lib.ptr(y1), _lib.ptr(d1),
                   w("cnn.weight"), n, T, F, _lib.ptr(dx), gr("cnn.weight"), gr("cnn.bias"), ws, wsn, st)
 
+    def _clip_setup(self):
+        """Buffers of the global-norm clip (clip_norm / adv_clip_norm): the fp64 partials of the gradient's sum
+        of squares, {norm before clipping, coefficient} as the clipped Adam leaves them on the device, and the
+        device counters of the updates refused for a non-finite gradient."""
+        dev = self.net.device
+        self.skipped_nonfinite = 0      # refused for a non-finite gradient, as check() has counted them
+        self.adv_skipped_nonfinite = 0  # the same for the Discriminator's updates
+        if self.clip_norm is not None:
+            self._clip_part = torch.zeros(ops.grad_sumsq_parts(self.net.grad.numel()), device=dev,
+                                          dtype=torch.float64)
+            self.grad_norm = torch.zeros(2, device=dev, dtype=torch.float32)
+            self._nonfinite = torch.zeros(1, device=dev, dtype=torch.int32)
+        if self.adv_clip_norm is not None:
+            self._adv_clip_part = torch.zeros(ops.grad_sumsq_parts(self.adversary.numel), device=dev,
+                                              dtype=torch.float64)
+            self.adv_grad_norm = torch.zeros(2, 2, device=dev, dtype=torch.float32)  # [grad_dis | grad_adv]
+            self._adv_nonfinite = torch.zeros(1, device=dev, dtype=torch.int32)
+
     def _adv_optimizer_step(self):
         """The Discriminator's updates, in the reference's order (dis.py:627-628, 646-647: one optimizer over
         both nets): Adam on grad_dis, then (disc_adv_update) Adam on grad_adv -- each a step of its own Adam
         state, guarded by the same status word as the separation net's."""
         D = self.adversary
-        for g in ((D.grad_dis, D.grad_adv) if self.disc_adv_update else (D.grad_dis,)):
+        for i, g in enumerate((D.grad_dis, D.grad_adv) if self.disc_adv_update else (D.grad_dis,)):
             self.adv_step_count += 1
+            if self.adv_clip_norm is not None:  # each update clipped on its own gradient
+                ops.grad_sumsq(g, self._adv_clip_part)
+                ops.adam_(D.flat, g, self.adv_m, self.adv_v, self.adv_step_count, self.adv_lr, self.betas, self.eps,
+                          status=self.status, loss=self.loss,
+                          clip=(self._adv_clip_part, self.adv_clip_norm, self.adv_grad_norm[i], self._adv_nonfinite))
+                continue
             _lib.call("dl4ss_adam_guarded", _lib.ptr(D.flat), _lib.ptr(g), _lib.ptr(self.adv_m), _lib.ptr(self.adv_v),
                       D.numel, float(self.adv_lr), float(self.betas[0]), float(self.betas[1]), float(self.eps),
                       self.adv_step_count, _lib.ptr(self.status), _lib.ptr(self.loss), _lib.stream_ptr())
@@ -1094,8 +1131,9 @@ class SepTrainer:
 
     def wait_allreduce(self):
         """The current stream waits for every all-reduce started this step: net.grad then holds the
-        gradient SUM over ranks (for callers that inspect or clip it before optimizer_step(), which
-        calls this itself; grad_mean() gives the mean)."""
+        gradient SUM over ranks (for callers that inspect it before optimizer_step(), which calls this
+        itself; grad_mean() gives the mean).  To clip the global norm, build the trainer with clip_norm:
+        the clip then runs on device inside optimizer_step(), with no pass over the gradient of its own."""
         for w in self._works:
             if w is not None:
                 w.wait()
@@ -1103,7 +1141,8 @@ class SepTrainer:
 
     def grad_mean(self):
         """The global-batch mean gradient (a new tensor): the all-reduced SUM x 1 / world, the
-        arithmetic the guarded Adam applies (gscale)."""
+        arithmetic the guarded Adam applies (gscale).  For inspection: clip_norm clips this gradient's
+        global norm without forming it, and leaves the norm in grad_norm."""
         self.wait_allreduce()
         return self.net.grad * (1.0 / self.world)
 
@@ -1113,15 +1152,28 @@ class SepTrainer:
         timed-out step never reaches the weights.  A refused step is counted on device
         (status[1]); check() takes the refused steps back out of step_count, so the bias
         corrections follow the updates actually applied, as torch.optim.Adam's do.  Data
-        parallel: the gradient is the SUM over ranks, scaled by 1 / world inside the update."""
+        parallel: the gradient is the SUM over ranks, scaled by 1 / world inside the update.
+
+        clip_norm: one sum-of-squares launch over net.grad (the all-reduced SUM, so every rank forms the
+        same coefficient), then the clipped Adam: the global-batch mean gradient's L2 norm is clipped to
+        clip_norm as torch.nn.utils.clip_grad_norm_ does, the factor folded into the 1 / world scale (no pass
+        that writes the gradient, no host sync); grad_norm holds {the norm before clipping, the coefficient}
+        afterwards (device, not synced).  A gradient with an Inf or NaN is refused like a timed-out step and
+        counted; check() rolls it out of step_count and adds it to skipped_nonfinite without raising.  The
+        Discriminator's updates run first and are guarded by adv_clip_norm alone: a non-finite separation
+        gradient does not undo them."""
         self.wait_allreduce()
         if self.adversary is not None:  # the Discriminator's updates first (the reference's order)
             self._adv_optimizer_step()
         self.step_count += 1
         shadow = self._shadow if (self._shadow_on and hasattr(self, "_shadow")) else None
+        clip = None
+        if self.clip_norm is not None:
+            ops.grad_sumsq(self.net.grad, self._clip_part)
+            clip = (self._clip_part, self.clip_norm, self.grad_norm, self._nonfinite)
         ops.adam_(self.net.flat, self.net.grad, self.m, self.v, self.step_count, self.lr, self.betas, self.eps,
                   status=self.status, loss=self.loss, dp_flag=self.net.dp_flag, gscale=1.0 / self.world,
-                  shadow=shadow)
+                  shadow=shadow, clip=clip)
         # the update bypasses torch's version counter: a new generation of the parameters, whose bf16
         # copies only this trainer holds (written by the same launch), and only if they were current
         # before it -- copies stale before the update stay stale after it
@@ -1244,14 +1296,34 @@ class SepTrainer:
         """Raise if a recurrence hand-off timed out, here or (data parallel) on a peer rank, since
         the last check: the guarded Adam already refused every update computed from then on.
         The refused steps are taken back out of step_count and the status word is reset, so the
-        trainer can continue after the caller has handled it."""
+        trainer can continue after the caller has handled it.
+
+        clip_norm / adv_clip_norm: updates refused only because their gradient held an Inf or NaN are
+        taken out of step_count (adv_step_count) in the same way and added to skipped_nonfinite
+        (adv_skipped_nonfinite); the device counters are reset and check() returns without raising.  As with
+        time-outs, the bias corrections of the steps enqueued before this check count the skipped step."""
         torch.cuda.synchronize()
         s, refused = (int(x) for x in self.status.tolist())
         if s or refused:
             self.status.zero_()
+            nf = nf_adv = 0
+            if self.clip_norm is not None:
+                nf = int(self._nonfinite.item())
+                self._nonfinite.zero_()
+            n_disc = (2 if self.disc_adv_update else 1) if self.adversary is not None else 0
+            if self.adv_clip_norm is not None:
+                nf_adv = int(self._adv_nonfinite.item())
+                self._adv_nonfinite.zero_()
+            # status[1] holds one count per timed-out step from the net's Adam and one from each clipped
+            # Discriminator update, plus the non-finite refusals (counted only on steps that did not time out)
+            timed_out = (refused - nf - nf_adv) // (1 + (n_disc if self.adv_clip_norm is not None else 0))
+            self.step_count -= timed_out + nf
+            self.skipped_nonfinite += nf
+            if self.adversary is not None:  # a timed-out step refused the Discriminator's updates too
+                self.adv_step_count -= timed_out * n_disc + nf_adv
+                self.adv_skipped_nonfinite += nf_adv
+            if not (s or timed_out):
+                return
             self.rnn_ws_all.zero_()  # a timed-out launch's half-written hand-offs must not reach the next
-            self.step_count -= refused
-            if self.adversary is not None:  # a refused step refused the Discriminator's updates too
-                self.adv_step_count -= refused * (2 if self.disc_adv_update else 1)
             where = "on this rank" if s else "on a data-parallel peer"
-            raise RuntimeError(f"BiRNN hand-off timed out {where} (status {s}): {refused} update(s) refused")
+            raise RuntimeError(f"BiRNN hand-off timed out {where} (status {s}): {timed_out} update(s) refused")

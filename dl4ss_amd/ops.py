@@ -340,8 +340,35 @@ def colsum(A, out):
     return out
 
 
+def grad_sumsq_parts(n):
+    """The number of fp64 partials grad_sumsq writes for n elements (1 .. 1024, a function of n alone)."""
+    return int(_lib.query("dl4ss_grad_sumsq_parts", int(n)))
+
+
+def grad_sumsq(g, part=None):
+    """part[j] = the fp64 sum of squares of the j-th fixed contiguous range of the flat fp32 gradient g
+    (grad_sumsq_parts(g.numel()) ranges; a fixed order, bitwise reproducible).  part.sum() is ||g||^2; the
+    clipped adam_ sums the partials itself."""
+    _f32c(g, "grad_sumsq")
+    n_part = grad_sumsq_parts(g.numel())
+    if part is None:
+        part = torch.empty(n_part, device=g.device, dtype=torch.float64)
+    if part.dtype != torch.float64 or part.numel() < n_part:
+        raise ValueError(f"grad_sumsq: part must hold {n_part} float64 values")
+    _lib.call("dl4ss_grad_sumsq", _lib.ptr(g), g.numel(), _lib.ptr(part), _lib.stream_ptr())
+    return part
+
+
+def check_clip_norm(x, name="clip_norm"):
+    """A clipping threshold as a float: positive (+inf allowed: measure and guard only), not NaN."""
+    x = float(x)
+    if not x > 0.0:  # also NaN
+        raise ValueError(f"{name} must be positive (inf allowed), got {x}")
+    return x
+
+
 def adam_(p, g, m, v, step, lr=2e-4, betas=(0.9, 0.999), eps=1e-8, status=None, loss=None, dp_flag=None, gscale=1.0,
-          shadow=None):
+          shadow=None, clip=None):
     """torch Adam step on flat buffers; with ``status`` (the recurrence hand-off status word,
     2 ints: {timed out, refused-update count}) the update is refused on device when a hand-off
     of this step timed out, loss[0] is set to NaN and status[1] counts the refusal
@@ -349,11 +376,31 @@ def adam_(p, g, m, v, step, lr=2e-4, betas=(0.9, 0.999), eps=1e-8, status=None, 
     behind the flat gradient) also when a data-parallel peer's hand-off timed out.  ``gscale``: the
     update uses g * gscale (1 / world_size on a SUM-reduced gradient; 1 is bitwise the unscaled step).
     ``shadow``: (nseg, seg_off, seg_rows, seg_cols, seg_y, seg_ldy) ctypes arrays -- bf16 copies of the
-    updated parameters written by the same launch (dl4ss_adam_guarded_dp_scaled_bf16)."""
+    updated parameters written by the same launch (dl4ss_adam_guarded_dp_scaled_bf16).
+    ``clip``: (part, max_norm, gnorm, nonfinite) -- the gradient's global norm clipped to max_norm
+    (dl4ss_adam_clipped): part = grad_sumsq(g), gnorm a float32[2] that receives {the norm of g * gscale, the
+    coefficient c} (or None), nonfinite an int32[1] that counts the updates refused because g held an Inf
+    or NaN (refused like a timed-out step: status[1] counts them too).  None: today's call, unchanged."""
     for t in (p, g, m, v):
         _f32c(t, "adam")
     if status is not None and status.numel() < 2:
         raise ValueError("adam_: the status word needs 2 ints (timed out, refused-update count)")
+    if clip is not None:
+        part, max_norm, gnorm, nonfinite = clip
+        max_norm = check_clip_norm(max_norm, "adam_: max_norm")
+        n_part = grad_sumsq_parts(p.numel())
+        if part.dtype != torch.float64 or part.numel() < n_part:
+            raise ValueError(f"adam_: clip needs the {n_part} float64 partials of grad_sumsq")
+        if gnorm is not None and (gnorm.dtype != torch.float32 or gnorm.numel() < 2):
+            raise ValueError("adam_: gnorm must hold 2 float32 values")
+        if nonfinite.dtype != torch.int32 or nonfinite.numel() < 1:
+            raise ValueError("adam_: nonfinite must be an int32 counter")
+        sh = shadow if shadow is not None else (0, None, None, None, None, None)
+        _lib.call("dl4ss_adam_clipped", _lib.ptr(p), _lib.ptr(g), _lib.ptr(m), _lib.ptr(v), p.numel(),
+                  float(lr), float(betas[0]), float(betas[1]), float(eps), int(step), _lib.ptr(status),
+                  _lib.ptr(dp_flag), float(gscale), _lib.ptr(loss), *sh, _lib.ptr(part), n_part, max_norm,
+                  _lib.ptr(gnorm), _lib.ptr(nonfinite), _lib.stream_ptr())
+        return
     if shadow is not None:
         _lib.call("dl4ss_adam_guarded_dp_scaled_bf16", _lib.ptr(p), _lib.ptr(g), _lib.ptr(m), _lib.ptr(v), p.numel(),
                   float(lr), float(betas[0]), float(betas[1]), float(eps), int(step), _lib.ptr(status),

@@ -406,6 +406,24 @@ int dl4ss_adam_guarded_dp_scaled_bf16(float* p, const float* g, float* m, float*
                                       float gscale, float* loss, int nseg, const long long* seg_off,
                                       const int* seg_rows, const int* seg_cols, void* const* seg_y,
                                       const long long* seg_ldy, void* stream);
+/* ---- global-norm gradient clipping (torch.nn.utils.clip_grad_norm_ on the global-batch mean gradient) ----
+ * The number of fp64 partials dl4ss_grad_sumsq writes for n elements: 1 .. 1024, a function of n alone
+ * (not of the device), so the same gradient gives the same bits on a full part and on a partition.  Host only. */
+long long dl4ss_grad_sumsq_parts(long long n);
+/* part[j] = the fp64 sum of g[i]^2 over the j-th fixed contiguous range of g (each element widened to fp64):
+ * a fixed order, no atomics, bitwise reproducible.  g must be 16-B aligned. */
+int dl4ss_grad_sumsq(const float* g, long long n, double* part, void* stream);
+/* dl4ss_adam_guarded_dp_scaled_bf16 on the clipped gradient.  From S = sum part[0 .. n_part), in fp64 on the
+ * device:  nrm = gscale sqrt(S);  c = min(1, max_norm / (nrm + 1e-6));  f = (float)(gscale c), used where
+ * gscale is (c == 1: bitwise the unclipped update; max_norm = +inf measures and guards only).  gnorm (2
+ * floats, may be NULL) receives {nrm, c}.  S not finite (an Inf or NaN in g): the update is refused as a
+ * timed-out one is (nothing changes, loss[0] = NaN, status[1] += 1) and nonfinite[0] += 1; a hand-off time-out
+ * (status[0], dp_flag) takes precedence and leaves nonfinite and gnorm alone.  part NULL: the unclipped entry. */
+int dl4ss_adam_clipped(float* p, const float* g, float* m, float* v, long long n, float lr, float beta1, float beta2,
+                       float eps, int step, int* status, const float* dp_flag, float gscale, float* loss, int nseg,
+                       const long long* seg_off, const int* seg_rows, const int* seg_cols, void* const* seg_y,
+                       const long long* seg_ldy, const double* part, int n_part, float max_norm, float* gnorm,
+                       int* nonfinite, void* stream);
 /* flag[0] = status[0] != 0 ? 1 : 0 (one float, written in front of the flat gradient before its all-reduce). */
 int dl4ss_status_flag(const int* status, float* flag, void* stream);
 
