@@ -107,6 +107,15 @@ SIGNATURES = {
     "dl4ss_mask_attn_loss_adv": [I, I, I, I, I, P, P, P, LL, P, LL, LL, P, F, F, P, P, P, LL, P, P, P, P, P],
     "dl4ss_mask_attn_loss_adv_bf16v": [I, I, I, I, I, P, P, P, LL, P, LL, LL, P, F, F, P, P, P, LL, P, P, P, P, P],
     "dl4ss_disc_adv_heads": [P, I, F, P, P, P, P],
+    "dl4ss_vp_compact": [P, I, I, I, I, F, P, P, P, P, P],
+    "dl4ss_vp_shift": [P, P, I, I, I, I, I, P, I, I, P],
+    "dl4ss_vp_mean_fwd": [P, I, I, I, P, P, P],
+    "dl4ss_vp_mean_bwd": [P, I, I, I, P, P, P],
+    "dl4ss_vp_colsum_parts": [LL],
+    "dl4ss_vp_colsum": [P, LL, I, P, P, P],
+    "dl4ss_spk_memory_fwd": [P, P, P, I, I, I, P, P, P],
+    "dl4ss_spk_memory_bwd": [P, P, P, P, P, I, I, I, P, P],
+    "dl4ss_spk_memory_store": [P, P, I, I, I, P, P, P],
 }
 # entry points that return a value rather than a hipError_t
 RESTYPES = {"dl4ss_birnn_workspace_bytes": ctypes.c_longlong, "dl4ss_colsum_bf16_part_bytes": ctypes.c_longlong,
@@ -114,7 +123,7 @@ RESTYPES = {"dl4ss_birnn_workspace_bytes": ctypes.c_longlong, "dl4ss_colsum_bf16
             "dl4ss_gemm_bf16_gl_grouped_ws_bytes": ctypes.c_longlong, "dl4ss_attn_nblk": ctypes.c_int,
             "dl4ss_attn_dot_nblk": ctypes.c_int, "dl4ss_attn_align_nblk": ctypes.c_int,
             "dl4ss_attn_align_part_floats": ctypes.c_longlong, "dl4ss_disc_ws_bytes": ctypes.c_longlong,
-            "dl4ss_debug_set_spin_limit": None,
+            "dl4ss_vp_colsum_parts": ctypes.c_longlong, "dl4ss_debug_set_spin_limit": None,
             "dl4ss_debug_set_place_force": None, "dl4ss_debug_set_rnn_max_wg": None}
 
 _lib = None

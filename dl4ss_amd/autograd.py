@@ -406,3 +406,39 @@ class DiscriminatorFn(torch.autograd.Function):
         dx, dw1, db1, dw2, db2, dw3, db3, dwf, dbf = disc_bwd_impl(dscore, spec, w1, w2, w3, wf, score, y1, y2, y3,
                                                                    ctx.precision, bool(ctx.needs_input_grad[0]))
         return dx, dw1, db1, dw2, db2, dw3, db3, dwf.view_as(wf), dbf, None
+
+
+# --------------------------------------------------------------------------- voiceprint encoder
+class VoiceprintFn(torch.autograd.Function):
+    """vec (n, E) = the masked voiceprint encoder of a VoiceprintNet over feats (n, T, F) (DL4SS_Keras/nnet.py:64-80:
+    Masking, the BiLSTM, MeanPool); differentiable in the net's flat parameter buffer (the gradient has its
+    layout).  lengths (n) int32 or None; rule / thr as ops.vp_compact."""
+
+    @staticmethod
+    def forward(ctx, feats, flat, vnet, lengths, rule, thr):
+        from .voiceprint import VoiceprintEncoder
+
+        if flat.data_ptr() != vnet.flat.data_ptr():
+            raise RuntimeError("VoiceprintFn: flat must be vnet.flat")
+        n, T, _ = feats.shape
+        enc = VoiceprintEncoder(vnet, n, T)
+        vec = enc.forward(_c(feats.float()), rule, thr, lengths).clone()
+        _check_status(enc.status[:1], "voiceprint forward")
+        ctx.enc = enc
+        return vec
+
+    @staticmethod
+    def backward(ctx, dvec):
+        enc = ctx.enc
+        keep, enc.net.grad = enc.net.grad, torch.zeros_like(enc.net.flat)
+        try:
+            g = enc.backward(_c(dvec.float()))
+        finally:
+            enc.net.grad = keep
+        _check_status(enc.status[:1], "voiceprint backward")
+        return None, g, None, None, None, None
+
+
+def voiceprint(feats, vnet, lengths=None, rule="nonzero", thr=None, flat=None):
+    """The voiceprints of feats (n, T, F) under autograd; ``flat``: vnet.flat as a leaf that requires grad."""
+    return VoiceprintFn.apply(feats, vnet.flat if flat is None else flat, vnet, lengths, rule, thr)

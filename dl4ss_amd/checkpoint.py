@@ -138,3 +138,25 @@ def save_reference_params(net, directory, tag, epoch):
         torch.save(sd, p)
         paths[kind] = p
     return paths
+
+
+def save_voiceprint(path, vnet, memory):
+    """The voiceprint encoder's parameters (``spk.layer.*``) and the speaker memory in one file: plain
+    ``torch.save`` of the two state dicts (the Keras tree's weights have no torch layout to mirror)."""
+    torch.save({"voiceprint": {k: v.cpu() for k, v in vnet.state_dict().items()},
+                "memory": {k: v.cpu() for k, v in memory.state_dict().items()}}, path)
+
+
+def load_voiceprint(path, vnet, memory):
+    """Load a save_voiceprint file into ``vnet`` and ``memory`` (in place; shapes must match)."""
+    sd = torch.load(path, map_location="cpu", weights_only=True)
+    if not isinstance(sd, dict) or set(sd) != {"voiceprint", "memory"}:
+        raise ValueError(f"{path}: not a save_voiceprint file")
+    for name, shape in vnet.specs:
+        if name not in sd["voiceprint"] or tuple(sd["voiceprint"][name].shape) != tuple(shape):
+            raise ValueError(f"{path}: {name} missing or not of shape {tuple(shape)}")
+    mem = sd["memory"].get("mem") if isinstance(sd["memory"], dict) else None
+    if mem is None or tuple(mem.shape) != (memory.M, memory.E):  # before either is written
+        raise ValueError(f"{path}: mem missing or not of shape {(memory.M, memory.E)}")
+    vnet.load_state_dict(sd["voiceprint"])
+    memory.load_state_dict(sd["memory"])

@@ -287,14 +287,27 @@ class SepTrainer:
     (torch.nn.utils.clip_grad_norm_'s arithmetic, on device; +inf measures and guards only) and refuse an update
     whose gradient holds an Inf or NaN; ``grad_norm`` (device float[2]) then holds the norm before clipping and the
     coefficient, ``skipped_nonfinite`` what check() has counted.  ``adv_clip_norm``: the same for each of the
-    Discriminator's updates (``adv_grad_norm``, float[2, 2]).  None (the default): no launch is added."""
+    Discriminator's updates (``adv_grad_norm``, float[2, 2]).  None (the default): no launch is added.
+
+    ``voiceprint`` (a ``voiceprint.VoiceprintNet``) with ``memory`` (a ``voiceprint.SpeakerMemory``): the queries
+    are not rows of ``emb.layer.weight`` but voiceprints -- the masked encoder over the step's own clean
+    magnitudes, accumulated into and read back from the speaker memory (DL4SS_Keras/nnet.py:64-92); the encoder
+    trains with the mask net (its own guarded Adam at ``voiceprint_lr``, default ``lr``) and the memory rows of
+    the batch's speakers are rewritten after every applied update: ``memory_refresh`` "reference" re-encodes
+    with the updated weights first (nnet.py:131-135), "reuse" stores the step's own queries.  fp32, mode
+    "label", single GPU, eager only; everything else is refused (_vp_refuse).  None (the default): no launch is
+    added and no line of the step changes."""
 
     def __init__(self, net, batch, k, n_samples, mode="label", precision="fp32", lr=2e-4, sum_weight=0.5,
                  loss_channels=None, betas=(0.9, 0.999), eps=1e-8, process_group=None, rnn_precision=None,
                  adversary=None, adv_weight=1.0, adv_lr=None, disc_adv_update=True, clip_norm=None,
-                 adv_clip_norm=None):
+                 adv_clip_norm=None, voiceprint=None, memory=None, voiceprint_lr=None, memory_refresh="reference"):
         if mode not in ("label", "pit", "crm"):
             raise ValueError(mode)
+        if voiceprint is not None or memory is not None:  # refused here, before any device call
+            self._vp_refuse(net, batch, k, mode, precision, loss_channels, process_group, adversary, clip_norm,
+                            voiceprint, memory, memory_refresh)
+        self.vnet, self.memory, self.memory_refresh = voiceprint, memory, memory_refresh
         # gradient clipping (_clip_setup): thresholds checked here, before any device call
         self.clip_norm = None if clip_norm is None else ops.check_clip_norm(clip_norm)
         self.adv_clip_norm = None if adv_clip_norm is None else ops.check_clip_norm(adv_clip_norm, "adv_clip_norm")
@@ -420,6 +433,8 @@ class SepTrainer:
         if adversary is not None:
             self._adv_setup(adv_weight, adv_lr, disc_adv_update)
         self._clip_setup()
+        if voiceprint is not None:
+            self._vp_setup(voiceprint_lr)
         if not self.fast:
             return
         # the bf16 step's operands, each produced directly as bf16 by the kernel that forms it (the BiRNN
@@ -468,8 +483,8 @@ class SepTrainer:
 
 
     # ------------------------------------------------------------------ features
-    def features(self, raw, gains):
-        ops.mix_sources(raw, gains, out_src=self.src, out_mix=self.mix, stats_ws=self.stats)
+    def features(self, raw, gains, lengths=None):
+        ops.mix_sources(raw, gains, out_src=self.src, out_mix=self.mix, stats_ws=self.stats, lengths=lengths)
         self._stfts()
 
     def _stfts(self):
@@ -619,6 +634,9 @@ class SepTrainer:
         else:
             ops.gemm(xin, w, transB=True, bias=net.view("mix.Linear.bias"), epilogue=ops.EPI_TANH, out=self.V,
                      precision=self.precision)
+        if self.vnet is not None:  # the queries are voiceprints read back from the speaker memory
+            self._vp_queries(self.q)
+            return
         wadj = net.view("adj.layer.weight") if net.adjust else None
         # (bf16: the time mean is already in self.mean, the query kernel reads no layer output)
         _lib.call("dl4ss_query_fwd", None if bf16v else _lib.ptr(self.out[-1]), B, T, 2 * H, _lib.ptr(self.spk),
@@ -1023,6 +1041,13 @@ class SepTrainer:
         last layer's output gradient."""
         net, B, T, H = self.net, self.B, self.T, self.net.H
         g = net.grad
+        if self.vnet is not None:
+            # dq -> the voiceprints' gradient through the memory, then the encoder's BPTT into vnet.grad (every
+            # element written); emb.layer.weight's gradient stays zero (backward_early zeroed it)
+            ops.spk_memory_bwd(self.dq.view(B * self.K, -1), self.vp_enc.vec, self.vp_u, self.spk.view(-1),
+                               self.memory.mem, dv=self.vp_dv)
+            self.vp_enc.backward(self.vp_dv)
+            return
         wadj = net.view("adj.layer.weight") if net.adjust else None
         _lib.call("dl4ss_query_bwd_ex", _lib.ptr(self.dq), B, T, 2 * H, _lib.ptr(self.spk),
                   _lib.ptr(net.view("emb.layer.weight")), _lib.ptr(wadj), _lib.ptr(self.mean), self.K, net.W,
@@ -1180,11 +1205,99 @@ class SepTrainer:
         fresh = shadow is not None and not self._wb_stale()
         self.net.params_changed()
         self._wb_ver = self._wb_key() if fresh else None
+        if self.vnet is not None:
+            self._vp_optimizer_step()
 
-    def step(self, raw, gains, spk_idx):
-        """One full training step on device-resident inputs; returns the loss tensor (not synced)."""
+    # ------------------------------------------------------------------ voiceprint queries
+    @staticmethod
+    def _vp_refuse(net, batch, k, mode, precision, loss_channels, process_group, adversary, clip_norm, vnet, memory,
+                   memory_refresh):
+        """Everything the voiceprint step is not built for, each with its reason (host checks only)."""
+        from .voiceprint import SpeakerMemory, VoiceprintNet
+
+        if vnet is None:
+            raise ValueError("memory: a SpeakerMemory needs voiceprint= (the encoder whose vectors it accumulates)")
+        if memory is None:
+            raise ValueError("voiceprint: the encoder needs memory= (a voiceprint.SpeakerMemory)")
+        if not isinstance(vnet, VoiceprintNet):
+            raise ValueError("voiceprint: expected a voiceprint.VoiceprintNet")
+        if not isinstance(memory, SpeakerMemory):
+            raise ValueError("memory: expected a voiceprint.SpeakerMemory")
+        if mode != "label":
+            raise ValueError(f"voiceprint: mode {mode!r} is unsupported, the enrolled query belongs to its own "
+                             "source (mode 'label')")
+        if net.crm:
+            raise ValueError("voiceprint: a cRM net (query width 2E) is unsupported")
+        if net.adjust:
+            raise ValueError("voiceprint: net.adjust is unsupported (ADDJUST adds to an embedding row, not to a "
+                             "memory row); build the SepNet with adjust=False")
+        if net.E != vnet.E:
+            raise ValueError(f"voiceprint: the encoder's vectors have {vnet.E} elements, the net's queries {net.E}")
+        if memory.E != vnet.E:
+            raise ValueError(f"memory: rows of {memory.E} elements, the encoder's vectors have {vnet.E}")
+        if net.F != vnet.F:
+            raise ValueError(f"voiceprint: the encoder reads {vnet.F} bins, the step's magnitudes have {net.F}")
+        if precision != "fp32":
+            raise ValueError(f"voiceprint: precision {precision!r} is unsupported, the voiceprint path is fp32")
+        if loss_channels:
+            raise ValueError("voiceprint: loss_channels is unsupported")
+        if adversary is not None:
+            raise ValueError("voiceprint: an adversary is unsupported")
+        if process_group is not None:
+            raise ValueError("voiceprint: no data-parallel voiceprint step (process_group; the encoder's gradient "
+                             "and the memory are not all-reduced)")
+        if clip_norm is not None:
+            raise ValueError("voiceprint: clip_norm is unsupported (one global norm over the two flat gradients "
+                             "needs a kernel change)")
+        if memory_refresh not in ("reference", "reuse"):
+            raise ValueError(f"memory_refresh {memory_refresh!r}: expected 'reference' or 'reuse'")
+        if batch * k > 1024:
+            raise ValueError(f"voiceprint: {batch * k} sources per step, the memory kernels take at most 1024")
+        dev = (net.device.type, net.device.index or 0)
+        for what, d in (("voiceprint", vnet.device), ("memory", memory.device)):
+            if (d.type, d.index or 0) != dev:
+                raise ValueError(f"{what}: lives on another device than the net")
+
+    def _vp_setup(self, voiceprint_lr):
+        from .voiceprint import VoiceprintEncoder
+
+        BK, E = self.B * self.K, self.vnet.E
+        f32 = dict(device=self.net.device, dtype=torch.float32)
+        self.vp_lr = self.lr if voiceprint_lr is None else voiceprint_lr
+        # the encoder over the step's B K clean magnitude maps; its recurrences share the step's status word
+        self.vp_enc = VoiceprintEncoder(self.vnet, BK, self.T, status=self.status)
+        self.vp_u = torch.empty(BK, E, **f32)
+        self.vp_dv = torch.empty(BK, E, **f32)
+        self.vp_q2 = torch.empty(BK, E, **f32)  # the refreshed rows ("reference")
+        self.vp_m = torch.zeros_like(self.vnet.flat)
+        self.vp_v = torch.zeros_like(self.vnet.flat)
+
+    def _vp_queries(self, q):
+        """q (B, K, E) = the memory rows of the step's speakers with this batch's unit voiceprints accumulated:
+        the masked encoder over the clean magnitudes the step's STFT wrote (silent frames, e.g. the zero tail of
+        a short source, are masked: rule 'nonzero'), then the memory forward.  (The STFT transforms frames in
+        pairs: a silent frame that shares its transform with a voiced one -- the first silent frame behind an odd
+        number of voiced ones -- carries that neighbour's rounding residue, ~1e-8 of it, and counts as valid.)"""
+        BK = self.B * self.K
+        vec = self.vp_enc.forward(self.mag_src.view(BK, self.T, self.F))
+        ops.spk_memory_fwd(vec, self.spk.view(-1), self.memory.mem, u=self.vp_u, q=q.view(BK, -1))
+
+    def _vp_optimizer_step(self):
+        """The encoder's guarded Adam (the same step count and status word: refused with the net's), then the
+        memory refresh, skipped on device when the update was refused."""
+        ops.adam_(self.vnet.flat, self.vnet.grad, self.vp_m, self.vp_v, self.step_count, self.vp_lr, self.betas,
+                  self.eps, status=self.status, loss=self.loss)
+        q = self.q
+        if self.memory_refresh == "reference":  # predict after train_on_batch (nnet.py:131-135)
+            q = self.vp_q2
+            self._vp_queries(q)
+        ops.spk_memory_store(q.view(self.B * self.K, -1), self.spk.view(-1), self.memory.mem, status=self.status)
+
+    def step(self, raw, gains, spk_idx, lengths=None):
+        """One full training step on device-resident inputs; returns the loss tensor (not synced).  lengths (B, K)
+        int32: each source's own length in samples (zero beyond: ops.mix_sources)."""
         self.spk.copy_(spk_idx)
-        self.features(raw, gains)
+        self.features(raw, gains, lengths)
         self.forward()
         loss = self.loss_and_grad()
         if self.buckets:
@@ -1223,7 +1336,8 @@ class SepTrainer:
     def capture(self):
         """Record STFT -> forward -> loss -> backward (~70 launches: persistent BiRNN
         kernels, gemm_gl GEMMs, attention, small kernels) as one HIP graph, replayed by
-        step_graph().  The mixing kernel (its input pointer changes per batch), the RCCL
+        step_graph() (not with voiceprint=: that step is eager only, NotImplementedError).  The mixing kernel (its
+        input pointer changes per batch), the RCCL
         all-reduce and Adam (its bias correction is a per-step host scalar) stay eager launches
         around the replay.  Bucketed data parallel: two graphs, split where the early bucket's
         all-reduce starts -- after the BPTT chain, which the side-stream dW_lin (forked and joined
@@ -1234,6 +1348,8 @@ class SepTrainer:
         step(), so every workspace exists before the capture."""
         import gc
 
+        if self.vnet is not None:
+            raise NotImplementedError("capture(): the voiceprint step is not built for HIP-graph capture; use step()")
         torch.cuda.synchronize()
         g = torch.cuda.CUDAGraph()
         g2 = torch.cuda.CUDAGraph() if self.buckets else None
@@ -1272,6 +1388,9 @@ class SepTrainer:
         """step() with the captured graph: mixing, graph replay, all-reduce, Adam (bucketed: the
         early bucket's all-reduce between the first two replays, the middle one's between the second
         and the third)."""
+        if self.vnet is not None:
+            raise NotImplementedError("step_graph(): the voiceprint step is not built for HIP-graph capture; "
+                                      "use step()")
         if getattr(self, "graph", None) is None:
             self.capture()
         self.spk.copy_(spk_idx)
@@ -1316,7 +1435,10 @@ class SepTrainer:
                 self._adv_nonfinite.zero_()
             # status[1] holds one count per timed-out step from the net's Adam and one from each clipped
             # Discriminator update, plus the non-finite refusals (counted only on steps that did not time out)
-            timed_out = (refused - nf - nf_adv) // (1 + (n_disc if self.adv_clip_norm is not None else 0))
+            # (the voiceprint encoder's Adam counts every refusal a second time; it runs with neither clip nor
+            # adversary)
+            timed_out = (refused - nf - nf_adv) // (1 + (n_disc if self.adv_clip_norm is not None else 0) +
+                                                    (1 if self.vnet is not None else 0))
             self.step_count -= timed_out + nf
             self.skipped_nonfinite += nf
             if self.adversary is not None:  # a timed-out step refused the Discriminator's updates too
@@ -1325,5 +1447,7 @@ class SepTrainer:
             if not (s or timed_out):
                 return
             self.rnn_ws_all.zero_()  # a timed-out launch's half-written hand-offs must not reach the next
+            if self.vnet is not None:
+                self.vp_enc.rnn_ws.zero_()
             where = "on this rank" if s else "on a data-parallel peer"
             raise RuntimeError(f"BiRNN hand-off timed out {where} (status {s}): {timed_out} update(s) refused")

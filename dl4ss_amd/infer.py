@@ -310,3 +310,72 @@ class RecursiveExtractor:
             st.check()
         return dict(spk=spk, masks=self.masks, step_pred=self.step_pred, probs=self.probs,
                     sort_index=self.sort_index)
+
+
+class EnrolledExtractor:
+    """Separation of speakers enrolled from clean speech (DL4SS_Keras/predict.py:160-180, 231-233): ``enrol``
+    turns clean excerpts into unit voiceprints with a ``voiceprint.VoiceprintNet``, ``run`` extracts one mask per
+    query from B mixtures of T frames with the mask net (``MaskNetForward`` and one attention launch per query
+    over the same V: 'dot' or 'align', as the net is built).  ``precision``: the mask net's, as MaskNetForward;
+    the voiceprint encoder is fp32."""
+
+    def __init__(self, net, vnet, B, T, K, precision="fp32"):
+        if net.crm:
+            raise ValueError("EnrolledExtractor: the magnitude-mask nets only (no cRM)")
+        if net.adjust:
+            raise ValueError("EnrolledExtractor: net.adjust (ADDJUST works on embedding rows, not on voiceprints)")
+        if net.E != vnet.E or net.F != vnet.F:
+            raise ValueError(f"EnrolledExtractor: the encoder gives ({vnet.F} bins -> {vnet.E}), the net takes "
+                             f"({net.F} bins, queries of {net.E})")
+        self.net, self.vnet, self.B, self.T, self.K = net, vnet, B, T, K
+        self.align = getattr(net, "attention", "dot") == "align"
+        self.mask_net = MaskNetForward(net, B, T, precision)
+        f32 = dict(device=net.device, dtype=torch.float32)
+        self.V = torch.empty(B * T, net.F * net.E, **f32)
+        self.masks = torch.empty(B, K, T, net.F, **f32)
+        self._enc = {}
+
+    def enrol(self, feats, rule="nonzero", thr=None, lengths=None):
+        """feats (n, T', F) clean features -> (n, E) unit voiceprints u = v / |v| (a new tensor): what a zero
+        memory row would return for the speaker."""
+        from .voiceprint import VoiceprintEncoder, unit
+
+        n, Te, _ = feats.shape
+        enc = self._enc.get((n, Te))
+        if enc is None:
+            enc = self._enc[(n, Te)] = VoiceprintEncoder(self.vnet, n, Te)
+        u = unit(enc.forward(feats.contiguous(), rule, thr, lengths))
+        enc.check()
+        return u
+
+    def run(self, feats, queries):
+        """feats (B, T, F) mixture magnitudes, queries (B, K, E) -> masks (B, K, T, F) (a buffer the next call
+        reuses)."""
+        B, K, net = self.B, self.K, self.net
+        R, E = self.T * net.F, net.E
+        q = queries.contiguous()
+        if tuple(q.shape) != (B, K, E) or q.dtype != torch.float32:
+            raise RuntimeError(f"EnrolledExtractor: queries {tuple(q.shape)}, expected float32 {(B, K, E)}")
+        V = self.mask_net(feats.contiguous(), self.V)
+        for k in range(K):
+            qk = ctypes.c_void_p(q.data_ptr() + 4 * k * E)
+            mk = ctypes.c_void_p(self.masks.data_ptr() + 4 * k * R)
+            if self.align:
+                _lib.call("dl4ss_attn_align_fwd", _lib.ptr(V), qk, K * E, _lib.ptr(net.view("att.Linear_1.weight")),
+                          _lib.ptr(net.view("att.Linear_2.weight")), _lib.ptr(net.view("att.Linear_3.weight")), B, R, E,
+                          mk, K * R, _lib.stream_ptr())
+            else:
+                _lib.call("dl4ss_attn_dot_fwd_ex", _lib.ptr(V), qk, K * E, B, R, E, 0, mk, K * R, _lib.stream_ptr())
+        self.mask_net.stack.check()
+        return self.masks
+
+    def queries_of(self, memory, ids):
+        """(B, K, E): the stored rows of the speakers ids (B, K) int32, re-normalised (-1: a zero query) -- the
+        seen-speaker path of predict.py:231-233, where an all-masked clean input adds nothing to the row."""
+        B, K = ids.shape
+        zero = torch.zeros(B * K, self.net.E, device=self.net.device, dtype=torch.float32)
+        return ops.spk_memory_fwd(zero, ids.reshape(-1).contiguous(), memory.mem)[0].view(B, K, -1)
+
+    def run_memory(self, feats, memory, ids):
+        """run() with the queries of the seen speakers ``ids`` (B, K) read from ``memory``."""
+        return self.run(feats, self.queries_of(memory, ids))

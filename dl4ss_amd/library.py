@@ -30,7 +30,10 @@ W2, w3)``                              DL4SS_Keras/extend_layers.py:50-64)
 ``dl4ss::discriminator(spec, w1, b1,   Discriminator: 3 x (Conv2d 3x3 stride 2 + ReLU), Linear,
 w2, b2, w3, b3, wf, bf, precision)``   sigmoid (main_run_sstune_dis.py:318-336); returns
                                        (score, y1, y2, y3)
+``dl4ss::spk_memory(v, ids, mem)``      speaker memory query (DL4SS_Keras/extend_layers.py:149-216)
 =====================================  ==========================================================
+
+The masked voiceprint encoder is the ``autograd.VoiceprintFn`` pair (its weights are one flat buffer).
 
 ``birnn_layer`` returns its saved activations as extra outputs (a custom op cannot stash
 tensors); ``birnn(x, ...)`` below returns the layer output only.
@@ -357,6 +360,44 @@ def _disc_backward(ctx, dscore, _dy1, _dy2, _dy3):
 discriminator.register_autograd(_disc_backward, setup_context=_disc_setup)
 
 
+# --------------------------------------------------------------------------- speaker memory
+@_op("spk_memory")
+def spk_memory(v: Tensor, ids: Tensor, mem: Tensor) -> Tensor:
+    """v (n, E) voiceprints, ids (n) int32, mem (M, E) -> q (n, E): each speaker's memory row with this batch's
+    unit voiceprints accumulated, re-normalised (mem is read only; it gets no gradient)."""
+    return ops.spk_memory_fwd(ag._c(v), ag._c(ids), ag._c(mem))[0]
+
+
+@spk_memory.register_fake
+def _(v, ids, mem):
+    return torch.empty_like(v, **F32)
+
+
+@_op("spk_memory_bwd")
+def spk_memory_bwd(dq: Tensor, v: Tensor, ids: Tensor, mem: Tensor) -> Tensor:
+    v, ids, mem = ag._c(v), ag._c(ids), ag._c(mem)
+    u = ops.spk_memory_fwd(v, ids, mem)[1]  # (a custom op cannot stash the unit vectors: formed again)
+    return ops.spk_memory_bwd(ag._c(dq), v, u, ids, mem)
+
+
+@spk_memory_bwd.register_fake
+def _(dq, v, ids, mem):
+    return torch.empty_like(v, **F32)
+
+
+def _spk_setup(ctx, inputs, output):
+    v, ids, mem = inputs
+    ctx.save_for_backward(v, ids, mem)
+
+
+def _spk_backward(ctx, dq):
+    v, ids, mem = ctx.saved_tensors
+    return spk_memory_bwd(dq.contiguous(), v, ids, mem), None, None
+
+
+spk_memory.register_autograd(_spk_backward, setup_context=_spk_setup)
+
+
 OPS = ("stft_mag", "stft_complex", "istft", "istft_apply", "mix_sources", "birnn_layer", "birnn_layer_bwd",
        "linear_tanh", "linear_tanh_bwd", "attention_dot", "attention_dot_bwd", "attention_align",
-       "attention_align_bwd", "top_k_mask", "discriminator", "discriminator_bwd")
+       "attention_align_bwd", "top_k_mask", "discriminator", "discriminator_bwd", "spk_memory", "spk_memory_bwd")

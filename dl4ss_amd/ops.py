@@ -484,3 +484,147 @@ def birnn_plan(cell, B, H, precision="bf16", max_wg=0):
     if rc != 0:
         return None
     return dict(zip(("BC", "NG", "J", "nchunk", "grid"), list(info)))
+
+
+# ---------------------------------------------------------------------------
+# voiceprint encoder / speaker memory (voiceprint.hip)
+# ---------------------------------------------------------------------------
+VP_RULES = {"nonzero": 0, "gt": 1}
+
+
+def _i32c(t, name, numel):
+    if not (t.is_cuda and t.dtype == torch.int32 and t.is_contiguous() and t.numel() == numel):
+        raise RuntimeError(f"{name}: expected a contiguous int32 CUDA tensor of {numel} elements")
+    return t
+
+
+def vp_compact(x, rule="nonzero", thr=None, lengths=None, xc=None, len_out=None, idx=None):
+    """x (n, T, F) -> (xc (n, T, F) the valid frames as a prefix, len (n) int32, idx (n, T) int32, -1 behind
+    len).  rule "nonzero": any bin != 0; "gt": any bin > thr; lengths (n) int32: a plain prefix instead."""
+    _f32c(x, "vp_compact")
+    if x.dim() != 3:
+        raise RuntimeError("vp_compact: expected (n, T, F)")
+    if rule not in VP_RULES:
+        raise ValueError(f"vp_compact: rule {rule!r}, expected one of {sorted(VP_RULES)}")
+    if rule == "gt" and thr is None and lengths is None:
+        raise ValueError("vp_compact: rule 'gt' needs thr")
+    n, T, F = x.shape
+    if lengths is not None:
+        _i32c(lengths, "vp_compact(lengths)", n)
+    i32 = dict(device=x.device, dtype=torch.int32)
+    xc = torch.empty_like(x) if xc is None else _f32c(xc, "vp_compact(xc)")
+    len_out = torch.empty(n, **i32) if len_out is None else _i32c(len_out, "vp_compact(len)", n)
+    idx = torch.empty(n, T, **i32) if idx is None else _i32c(idx, "vp_compact(idx)", n * T)
+    if xc.numel() != x.numel():
+        raise RuntimeError("vp_compact: xc must have x's size")
+    _lib.call("dl4ss_vp_compact", _lib.ptr(x), n, T, F, VP_RULES[rule], float(0.0 if thr is None else thr),
+              _lib.ptr(lengths), _lib.ptr(xc), _lib.ptr(len_out), _lib.ptr(idx), _lib.stream_ptr())
+    return xc, len_out, idx
+
+
+def vp_shift(src, dst, lengths, c0, c1, direction, other=0):
+    """dst (n, T, ld)[:, :, c0:c1] = src's rows moved by +(T - len) (direction +1, zero fill in front) or back
+    (-1, zero rows behind len); the other columns: other 0 untouched, 1 src on rows < len and zero behind,
+    2 src."""
+    _f32c(src, "vp_shift(src)")
+    _f32c(dst, "vp_shift(dst)")
+    if src.dim() != 3 or src.shape != dst.shape:
+        raise RuntimeError("vp_shift: src and dst must be (n, T, ld) of one shape")
+    n, T, ld = src.shape
+    _i32c(lengths, "vp_shift(lengths)", n)
+    _lib.call("dl4ss_vp_shift", _lib.ptr(src), _lib.ptr(dst), n, T, ld, int(c0), int(c1), _lib.ptr(lengths),
+              int(direction), int(other), _lib.stream_ptr())
+    return dst
+
+
+def vp_mean_fwd(out, lengths, vec=None):
+    """out (n, T, 2H) in the recurrence's frame -> vec (n, 2H): each utterance's mean over its own frames."""
+    _f32c(out, "vp_mean_fwd")
+    n, T, D = out.shape
+    _i32c(lengths, "vp_mean_fwd(lengths)", n)
+    vec = torch.empty(n, D, device=out.device, dtype=torch.float32) if vec is None else _f32c(vec, "vp_mean_fwd(vec)")
+    if D % 2 or vec.numel() != n * D:
+        raise RuntimeError("vp_mean_fwd: out (n, T, 2H), vec (n, 2H)")
+    _lib.call("dl4ss_vp_mean_fwd", _lib.ptr(out), n, T, D // 2, _lib.ptr(lengths), _lib.ptr(vec), _lib.stream_ptr())
+    return vec
+
+
+def vp_mean_bwd(dvec, lengths, dout):
+    """dvec (n, 2H) -> dout (n, T, 2H), every element written."""
+    _f32c(dvec, "vp_mean_bwd")
+    _f32c(dout, "vp_mean_bwd(dout)")
+    n, T, D = dout.shape
+    _i32c(lengths, "vp_mean_bwd(lengths)", n)
+    if D % 2 or dvec.numel() != n * D:
+        raise RuntimeError("vp_mean_bwd: dvec (n, 2H), dout (n, T, 2H)")
+    _lib.call("dl4ss_vp_mean_bwd", _lib.ptr(dvec), n, T, D // 2, _lib.ptr(lengths), _lib.ptr(dout), _lib.stream_ptr())
+    return dout
+
+
+def vp_colsum_part(M, C, device):
+    """The partial-sum buffer vp_colsum needs for an (M, C) matrix."""
+    P = _lib.query("dl4ss_vp_colsum_parts", int(M))
+    if P < 0:
+        raise RuntimeError(f"vp_colsum: M = {M} unsupported")
+    return torch.empty(P * C, device=device, dtype=torch.float32)
+
+
+def vp_colsum(A, out, part):
+    """out (C) = column sums of the contiguous A (M, C) in a fixed order for any M (two stages through ``part``,
+    no atomics: the same input gives the same bits); every element of out written."""
+    _f32c(A, "vp_colsum")
+    _f32c(out, "vp_colsum(out)")
+    _f32c(part, "vp_colsum(part)")
+    if A.dim() != 2 or out.numel() != A.shape[1]:
+        raise RuntimeError("vp_colsum: A (M, C), out (C)")
+    M, C = A.shape
+    if part.numel() < _lib.query("dl4ss_vp_colsum_parts", M) * C:
+        raise RuntimeError("vp_colsum: part too small (ops.vp_colsum_part)")
+    _lib.call("dl4ss_vp_colsum", _lib.ptr(A), M, C, _lib.ptr(part), _lib.ptr(out), _lib.stream_ptr())
+    return out
+
+
+def _spk_args(v, ids, mem, name):
+    _f32c(v, name)
+    _f32c(mem, f"{name}(mem)")
+    if v.dim() != 2 or mem.dim() != 2 or mem.shape[1] != v.shape[1]:
+        raise RuntimeError(f"{name}: v (n, E) and mem (M, E)")
+    n, E = v.shape
+    if n > 1024 or E > 128:
+        raise RuntimeError(f"{name}: n <= 1024 and E <= 128")
+    _i32c(ids, f"{name}(ids)", n)
+    return n, E, mem.shape[0]
+
+
+def spk_memory_fwd(v, ids, mem, u=None, q=None):
+    """v (n, E), ids (n) int32, mem (M, E) -> (q (n, E) the speakers' normalised memory rows with this batch's
+    unit voiceprints accumulated, u (n, E) the unit voiceprints).  mem is only read."""
+    n, E, M = _spk_args(v, ids, mem, "spk_memory_fwd")
+    u = torch.empty_like(v) if u is None else _f32c(u, "spk_memory_fwd(u)")
+    q = torch.empty_like(v) if q is None else _f32c(q, "spk_memory_fwd(q)")
+    if u.numel() != n * E or q.numel() != n * E:
+        raise RuntimeError("spk_memory_fwd: u and q must be (n, E)")
+    _lib.call("dl4ss_spk_memory_fwd", _lib.ptr(v), _lib.ptr(ids), _lib.ptr(mem), n, E, M, _lib.ptr(u), _lib.ptr(q),
+              _lib.stream_ptr())
+    return q, u
+
+
+def spk_memory_bwd(dq, v, u, ids, mem, dv=None):
+    """dq (n, E) -> dv (n, E) (v, ids, mem as given to spk_memory_fwd, u as it wrote it)."""
+    n, E, M = _spk_args(v, ids, mem, "spk_memory_bwd")
+    _f32c(dq, "spk_memory_bwd(dq)")
+    _f32c(u, "spk_memory_bwd(u)")
+    dv = torch.empty_like(v) if dv is None else _f32c(dv, "spk_memory_bwd(dv)")
+    if dq.numel() != n * E or u.numel() != n * E or dv.numel() != n * E:
+        raise RuntimeError("spk_memory_bwd: dq, u and dv must be (n, E)")
+    _lib.call("dl4ss_spk_memory_bwd", _lib.ptr(dq), _lib.ptr(v), _lib.ptr(u), _lib.ptr(ids), _lib.ptr(mem), n, E, M,
+              _lib.ptr(dv), _lib.stream_ptr())
+    return dv
+
+
+def spk_memory_store(q, ids, mem, status=None):
+    """mem[ids[i]] = q[i] (ids outside [0, M) skipped); with ``status`` nothing is stored when status[0] != 0."""
+    n, E, M = _spk_args(q, ids, mem, "spk_memory_store")
+    _lib.call("dl4ss_spk_memory_store", _lib.ptr(q), _lib.ptr(ids), n, E, M, _lib.ptr(mem), _lib.ptr(status),
+              _lib.stream_ptr())
+    return mem

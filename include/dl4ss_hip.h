@@ -563,6 +563,54 @@ int dl4ss_disc_conv64_bwd(int prec, const void* x, const void* y, const void* dy
 int dl4ss_disc_conv1_bwd(int prec, const float* x, const void* y1, const void* dy1, const float* w, int N, int T,
                          int F, float* dx, float* dw, float* db, void* ws, long long ws_bytes, void* stream);
 
+/* ---- voiceprint encoder and speaker memory (Cocktail/software/DL4SS_Keras/nnet.py:64-92,
+ *      extend_layers.py:105-228): a speaker enrolled from clean speech.  fp32; no atomics, every sum in a
+ *      fixed order (repeatable bit for bit); sizes are checked before any device call. ---- */
+/* Frame mask and compaction.  x (n, T, F) -> xc (n, T, F): utterance b's valid frames in their own order as
+ * rows [0, len[b]), zero rows behind; len (n) int32; idx (n, T) int32, idx[b, j] = the j-th valid frame, -1
+ * for j >= len[b].  rule 0: a frame is valid when any bin != 0 (Masking(0.), nnet.py:46); rule 1: when any
+ * bin > thr (MaskingGt, nnet.py:44; the caller passes log features, no logarithm is taken here).  len_in (n,
+ * NULL: none) overrides the rule with the prefix [0, len_in[b]) (clamped to [0, T]).  T <= 2048; xc != x. */
+int dl4ss_vp_compact(const float* x, int n, int T, int F, int rule, float thr, const int* len_in, float* xc,
+                     int* len, int* idx, void* stream);
+/* Row shift of the columns [c0, c1) of src (n, T, ld) into dst (same shape, dst != src) by d = T - len[b]:
+ * dir +1: dst row t = src row t - d, rows < d zero (compact frame -> right-aligned, the frame in which the
+ * full-length recurrence starts an utterance's reverse pass at its own last frame); dir -1: dst row t = src
+ * row t + d, rows >= len[b] zero (back).  The other columns of dst: other 0 untouched, 1 = src on rows < len[b]
+ * and zero beyond, 2 = src -- one launch assembles the next layer's input, or moves one direction of G / dG. */
+int dl4ss_vp_shift(const float* src, float* dst, int n, int T, int ld, int c0, int c1, const int* len, int dir,
+                   int other, void* stream);
+/* Masked mean (MeanPool, extend_layers.py:105-125) of a layer output out (n, T, 2H) in the recurrence's frame:
+ * vec (n, 2H) = sum / (len + 2.22e-16) over the forward half's rows [0, len) and the reverse half's rows
+ * [T - len, T), in ascending t; len 0 gives zeros. */
+int dl4ss_vp_mean_fwd(const float* out, int n, int T, int H, const int* len, float* vec, void* stream);
+/* Its backward: every element of dOut (n, T, 2H) written, dvec / (len + 2.22e-16) on the rows the mean read
+ * and zero elsewhere (the BPTT then yields a dG that is exactly zero on the padded rows). */
+int dl4ss_vp_mean_bwd(const float* dvec, int n, int T, int H, const int* len, float* dOut, void* stream);
+/* Column sums in a fixed order for any row count (the encoder's bias gradient colsum(dG); dl4ss_colsum adds
+ * its row blocks atomically): out (C) = sum over the M rows of the contiguous A (M, C).  Blocks of 64 rows are
+ * summed in ascending row into part (dl4ss_vp_colsum_parts(M) * C floats), then the parts in ascending block;
+ * the same input gives the same bits.  Every element of out is written.  1 <= M <= 65535 * 64 (the parts query
+ * returns -1 outside). */
+long long dl4ss_vp_colsum_parts(long long M);
+int dl4ss_vp_colsum(const float* A, long long M, int C, float* part, float* out, void* stream);
+/* Speaker memory forward (extend_layers.py:149-179).  v (n, E) voiceprints, ids (n) int32, mem (M, E), read
+ * only:  u_i = v_i / |w(v_i)|, w(a) = a with 2.22e-16 where a == 0;  A = mem, A[ids[i]] += u_i in ascending i
+ * (duplicate ids accumulate, as inc_subtensor);  q_i = A[ids[i]] / |w(A[ids[i]])|.  An id outside [0, M) (-1:
+ * no speaker) gives a zero query and adds nothing.  u (n, E) and q (n, E) are written; only the rows the
+ * batch touches are formed.  n <= 1024, E <= 128; one workgroup. */
+int dl4ss_spk_memory_fwd(const float* v, const int* ids, const float* mem, int n, int E, int M, float* u, float* q,
+                         void* stream);
+/* Its backward: dv (n, E) from dq (n, E), with v, ids, mem as given to the forward and the u it wrote.  The
+ * switch passes no gradient to its constant branch; mem gets none (trainable=False). */
+int dl4ss_spk_memory_bwd(const float* dq, const float* v, const float* u, const int* ids, const float* mem, int n,
+                         int E, int M, float* dv, void* stream);
+/* update_memory (extend_layers.py:220-228): mem[ids[i]] = q_i (duplicates carry identical rows, ids outside
+ * [0, M) are skipped).  status (NULL: none): the recurrence status word; status[0] != 0 (the guarded Adam
+ * refused this step) leaves mem untouched. */
+int dl4ss_spk_memory_store(const float* q, const int* ids, int n, int E, int M, float* mem, const int* status,
+                           void* stream);
+
 /* ---- BSS-eval (replaces the un-vendored separation.bss_eval_sources of
  *      Torch_multi/bss_test.py:5,55 -- BSS_EVAL v3, 512-tap distortion filters) ---- */
 /* R (M,P,P,L) fp64: R[m][a][b][l] = sum_n x[m][a][n] x[m][b][n+l], l < L, x (M,P,N) fp32
