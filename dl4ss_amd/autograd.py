@@ -338,19 +338,12 @@ def disc_fwd_impl(spec, w1, b1, w2, b2, w3, b3, wf, bf, precision):
     feat, hw = disc_dims(T, F)
     if wf.numel() != feat:
         raise RuntimeError(f"Discriminator: final.weight has {wf.numel()} features, a ({T}, {F}) map gives {feat}")
-    prec, dt, dev, st = ops.PREC[precision], _disc_act_dtype(precision), spec.device, _lib.stream_ptr()
-    y1, y2, y3 = (torch.empty(N, hw[2 * l], hw[2 * l + 1], 64, dtype=dt, device=dev) for l in range(3))
-    _lib.call("dl4ss_disc_conv1_fwd", prec, _lib.ptr(spec), _lib.ptr(_c(w1)), _lib.ptr(_c(b1)), N, T, F, _lib.ptr(y1),
-              st)
-    _lib.call("dl4ss_disc_conv64_fwd", prec, _lib.ptr(y1), _lib.ptr(_c(w2)), _lib.ptr(_c(b2)), N, hw[0], hw[1],
-              _lib.ptr(y2), st)
-    _lib.call("dl4ss_disc_conv64_fwd", prec, _lib.ptr(y2), _lib.ptr(_c(w3)), _lib.ptr(_c(b3)), N, hw[2], hw[3],
-              _lib.ptr(y3), st)
-    z = torch.empty(N, device=dev)
+    dt, dev = _disc_act_dtype(precision), spec.device
+    ys = [torch.empty(N, hw[2 * l], hw[2 * l + 1], 64, dtype=dt, device=dev) for l in range(3)]
     score = torch.empty(N, 1, device=dev)
-    _lib.call("dl4ss_disc_head_fwd", prec, _lib.ptr(y3), _lib.ptr(_c(wf)), _lib.ptr(_c(bf)), N, hw[4], hw[5],
-              _lib.ptr(z), _lib.ptr(score), st)
-    return score, y1, y2, y3
+    ops.disc_forward(ops.PREC[precision], spec, [_c(p) for p in (w1, b1, w2, b2, w3, b3, wf, bf)], ys,
+                     torch.empty(N, device=dev), score)
+    return (score, *ys)
 
 
 def disc_bwd_impl(dscore, spec, w1, w2, w3, wf, score, y1, y2, y3, precision, need_dx=True, target=None):
@@ -358,32 +351,23 @@ def disc_bwd_impl(dscore, spec, w1, w2, w3, wf, score, y1, y2, y3, precision, ne
     head fuses the loss mean_n (score_n - target)^2 (target 1 or 0) and its scalar is appended to the result."""
     spec = _c(spec.float())
     N, T, F = spec.shape
-    _, hw = disc_dims(T, F)
-    prec, dev, st = ops.PREC[precision], spec.device, _lib.stream_ptr()
+    disc_dims(T, F)
+    dev = spec.device
     w1, w2, w3, wf = _c(w1), _c(w2), _c(w3), _c(wf)
     wsn = _lib.query("dl4ss_disc_ws_bytes", N, T, F)
     if wsn < 0:
         raise RuntimeError(f"Discriminator shape unsupported (N={N}, T={T}, F={F})")
     ws = torch.empty((wsn + 3) // 4, device=dev)
     dz = torch.empty(N, device=dev)
-    dwf, dbf = torch.empty_like(wf), torch.empty(1, device=dev)
-    dw1, dw2, dw3 = torch.empty_like(w1), torch.empty_like(w2), torch.empty_like(w3)
-    db1, db2, db3 = (torch.empty(64, device=dev) for _ in range(3))
-    dy3, dy2, dy1 = torch.empty_like(y3), torch.empty_like(y2), torch.empty_like(y1)
+    grads = [torch.empty_like(w) if b is None else torch.empty(b, device=dev)  # dw1, db1, ..., dwf, dbf
+             for w, n in ((w1, 64), (w2, 64), (w3, 64), (wf, 1)) for b in (None, n)]
     loss = torch.empty(1, device=dev) if dscore is None else None
-    ds = _c(dscore.float()) if dscore is not None else None
-    _lib.call("dl4ss_disc_head_bwd", prec, _lib.ptr(y3), _lib.ptr(wf), _lib.ptr(_c(score)), _lib.ptr(ds),
-              float(target if target is not None else 0.0), N, hw[4], hw[5], _lib.ptr(loss), _lib.ptr(dz),
-              _lib.ptr(dwf), _lib.ptr(dbf), _lib.ptr(dy3), st)
-    _lib.call("dl4ss_disc_conv64_bwd", prec, _lib.ptr(y2), _lib.ptr(y3), _lib.ptr(dy3), _lib.ptr(w3), N, hw[2], hw[3],
-              _lib.ptr(dy2), _lib.ptr(dw3), _lib.ptr(db3), _lib.ptr(ws), wsn, st)
-    _lib.call("dl4ss_disc_conv64_bwd", prec, _lib.ptr(y1), _lib.ptr(y2), _lib.ptr(dy2), _lib.ptr(w2), N, hw[0], hw[1],
-              _lib.ptr(dy1), _lib.ptr(dw2), _lib.ptr(db2), _lib.ptr(ws), wsn, st)
     dx = torch.empty_like(spec) if need_dx else None
-    _lib.call("dl4ss_disc_conv1_bwd", prec, _lib.ptr(spec), _lib.ptr(y1), _lib.ptr(dy1), _lib.ptr(w1), N, T, F,
-              _lib.ptr(dx), _lib.ptr(dw1), _lib.ptr(db1), _lib.ptr(ws), wsn, st)
-    out = (dx, dw1, db1, dw2, db2, dw3, db3, dwf, dbf.view(1))
-    return out if dscore is not None else out + (loss[0],)
+    ops.disc_backward(ops.PREC[precision], spec, (w1, w2, w3, wf), (y1, y2, y3),
+                      [torch.empty_like(y) for y in (y1, y2, y3)], _c(score),
+                      _c(dscore.float()) if dscore is not None else None, target if target is not None else 0.0, loss,
+                      dz, grads, dx, ws, wsn)
+    return (dx, *grads) if dscore is not None else (dx, *grads, loss[0])
 
 
 class DiscriminatorFn(torch.autograd.Function):

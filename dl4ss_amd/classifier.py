@@ -15,7 +15,7 @@ guarded Adam (``optimizer_step``).  Single GPU, eager launches (no HIP-graph cap
 """
 import torch
 
-from . import _lib, ops
+from . import _lib, adam, ops
 
 LSTM = 0
 
@@ -37,7 +37,6 @@ class ClassifierTrainer:
         self.clip_norm = None if clip_norm is None else ops.check_clip_norm(clip_norm)
         self.net, self.B, self.K, self.N = cnet, batch, k, n_samples
         self.precision = precision
-        self.lr, self.betas, self.eps = lr, betas, eps
         B, K, N, H, L, C = batch, k, n_samples, cnet.H, cnet.L, cnet.num_labels
         self.T = T = ops.n_frames(n_samples)
         self.F = F = cnet.F
@@ -71,14 +70,15 @@ class ClassifierTrainer:
         self.rnn_ws = torch.zeros((ws + 7) // 8, device=dev, dtype=torch.int64)
         self.status = torch.zeros(2, device=dev, dtype=torch.int32)  # {hand-off timed out, refused updates}
         cnet.grad = torch.zeros_like(cnet.flat)
-        self.m = torch.zeros_like(cnet.flat)
-        self.v = torch.zeros_like(cnet.flat)
-        self.step_count = 0
-        self.skipped_nonfinite = 0  # updates refused for a non-finite gradient (counted by check())
+        self.opt = adam.GuardedAdam(cnet.flat, self.status, self.loss, lr, betas, eps, clip_norm=self.clip_norm)
+        self.m, self.v = self.opt.m, self.opt.v
         if self.clip_norm is not None:
-            self._clip_part = torch.zeros(ops.grad_sumsq_parts(cnet.flat.numel()), device=dev, dtype=torch.float64)
-            self.grad_norm = torch.zeros(2, **f32)
-            self._nonfinite = torch.zeros(1, device=dev, dtype=torch.int32)
+            self.grad_norm = self.opt.grad_norm
+
+    # the documented scalars live in the optimizer, read / write (schedule.classifier() assigns lr)
+    lr = adam.delegate("opt", "lr")
+    step_count = adam.delegate("opt", "step_count")
+    skipped_nonfinite = adam.delegate("opt", "skipped_nonfinite")  # counted by check()
 
     # ------------------------------------------------------------------ features
     def features(self, raw=None, gains=None, feats=None):
@@ -156,13 +156,7 @@ class ClassifierTrainer:
         """Adam on the flat buffers; refused on device (parameters untouched, loss[0] = NaN, status[1]
         counts it) when a recurrence hand-off of this step timed out.  With clip_norm: one sum-of-squares
         launch first, then the clipped Adam, which also refuses a gradient that holds an Inf or NaN."""
-        self.step_count += 1
-        clip = None
-        if self.clip_norm is not None:
-            ops.grad_sumsq(self.net.grad, self._clip_part)
-            clip = (self._clip_part, self.clip_norm, self.grad_norm, self._nonfinite)
-        ops.adam_(self.net.flat, self.net.grad, self.m, self.v, self.step_count, self.lr, self.betas, self.eps,
-                  status=self.status, loss=self.loss, clip=clip)
+        self.opt.step(self.net.grad)
 
     def step(self, raw=None, gains=None, y_map=None, feats=None):
         """One training step on device-resident inputs; returns the loss tensor (not synced)."""
@@ -182,13 +176,10 @@ class ClassifierTrainer:
         non-finite alike."""
         torch.cuda.synchronize()
         s, refused = (int(x) for x in self.status.tolist())
-        nonfinite = int(self._nonfinite.item()) if self.clip_norm is not None else 0
         if s or refused:
             self.status.zero_()
-            self.step_count -= refused
-            if nonfinite:
-                self._nonfinite.zero_()
-                self.skipped_nonfinite += nonfinite
-            if s or refused > nonfinite:
+            timed_out = adam.timed_out_steps(refused, [(self.opt, 1)])
+            self.opt.settle(timed_out)
+            if s or timed_out:
                 self.rnn_ws.zero_()
-                raise RuntimeError(f"BiRNN hand-off timed out (status {s}): {refused - nonfinite} update(s) refused")
+                raise RuntimeError(f"BiRNN hand-off timed out (status {s}): {timed_out} update(s) refused")

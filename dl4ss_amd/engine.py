@@ -16,268 +16,15 @@ reference / oracle state dict loads directly) and all gradients in a second
 flat buffer: one all-reduce and one Adam launch per step.
 """
 import ctypes
-import math
-import os
-import types
 
 import torch
 
-from . import _lib, ops
+from . import _lib, adam, dp, ops
+from .adversarial import AdvStep
 from .ops import CELLS, DEFER_BIAS, DGH_PAD8, DOUT_SLABS, WS_ZEROED, pad8  # noqa: F401 (re-exported)
-
-
-def _ngate(cell):
-    return 4 if cell == "lstm" else 3
-
-
-class FlatParams:
-    """Parameters in one flat fp32 buffer with named views (16-B aligned) under the reference's
-    ``state_dict`` key names; ``layer_prefix`` + ``{kind}_l{l}[_reverse]`` names the recurrent layers'."""
-
-    layer_prefix = "layer."
-
-    def _layer_specs(self, num_layers, input_fre, hidden, NGH):
-        specs = []
-        for l in range(num_layers):
-            D = input_fre if l == 0 else 2 * hidden
-            for kind, shape in (("weight_ih", (NGH, D)), ("weight_hh", (NGH, hidden)), ("bias_ih", (NGH,)),
-                                ("bias_hh", (NGH,))):
-                specs.append((f"{self.layer_prefix}{kind}_l{l}", shape))
-                specs.append((f"{self.layer_prefix}{kind}_l{l}_reverse", shape))
-        return specs
-
-    def _allocate(self, specs, device):
-        self.specs = specs
-        self.offsets = {}
-        off = 0
-        for name, shape in specs:
-            self.offsets[name] = (off, shape)
-            off += (math.prod(shape) + 3) // 4 * 4  # 16-B aligned views
-        self.numel = off
-        self.device = torch.device(device)
-        self.flat = torch.zeros(off, device=self.device, dtype=torch.float32)
-
-    def view(self, name, buf=None):
-        """The parameter ``name``, or its counterpart in ``buf`` (a flat buffer of the same layout:
-        the gradient, an Adam moment)."""
-        off, shape = self.offsets[name]
-        return (self.flat if buf is None else buf)[off:off + math.prod(shape)].view(shape)
-
-    def cat_view(self, kind, l, buf=None):
-        """[fwd; reverse] of layer l (adjacent in the flat buffer by construction)."""
-        off, shape = self.offsets[f"{self.layer_prefix}{kind}_l{l}"]
-        v = (self.flat if buf is None else buf)[off:off + 2 * math.prod(shape)]
-        return v.view(2 * shape[0], *shape[1:])
-
-    def load_state_dict(self, sd):
-        for name, _ in self.specs:
-            self.view(name).copy_(sd[name].to(torch.float32))
-
-    def state_dict(self):
-        return {name: self.view(name).detach().clone() for name, _ in self.specs}
-
-
-class SepNet(FlatParams):
-    """Trainable parameters of the mask network, flat fp32 with named views."""
-
-    layer_prefix = "mix.layer."
-
-    def __init__(self, cell="lstm", num_layers=4, hidden=300, emb=50, num_labels=101, input_fre=129, crm=False,
-                 adjust=True, device="cuda", seed=1, attention="dot"):
-        if attention not in ("dot", "align"):
-            raise ValueError(f"attention={attention!r}: expected 'dot' or 'align'")
-        if attention == "align" and crm:
-            raise ValueError("attention='align' with a cRM net is unsupported (the reference never ran that pair)")
-        # 'dot': mask = sigmoid(V . q); 'align': sigmoid(w3 . tanh(W1 V + W2 q)) on the three extra
-        # ATTENTION weights (EvalVer.py:228-239; DL4SS_Keras/extend_layers.py:50-64)
-        self.attention = attention
-        self.cell, self.L, self.H, self.E = cell, num_layers, hidden, emb
-        self.F, self.num_labels, self.crm, self.adjust = input_fre, num_labels, crm, adjust
-        self.W = 2 * emb if crm else emb
-        specs = self._layer_specs(num_layers, input_fre, hidden, _ngate(cell) * hidden)
-        specs += [("mix.Linear.weight", (input_fre * emb, 2 * hidden)), ("mix.Linear.bias", (input_fre * emb,)),
-                  ("emb.layer.weight", (num_labels, self.W))]
-        if adjust:
-            specs.append(("adj.layer.weight", (self.W, 2 * hidden + self.W)))
-        if attention == "align":  # behind every 'dot' parameter: the default layout does not move
-            specs += [("att.Linear_1.weight", (emb, emb)), ("att.Linear_2.weight", (emb, emb)),
-                      ("att.Linear_3.weight", (1, emb))]
-        self._allocate(specs, device)
-        off = self.numel
-        # the flat gradient behind one 16-B slot: slot 0 carries each rank's hand-off status flag
-        # through the gradient all-reduce (SepTrainer.allreduce), so every rank's guarded Adam
-        # refuses the same steps.  Layout [flag | layers | Linear, emb, adj]: the data-parallel
-        # step's two buckets are the contiguous ranges in front of and behind the Linear weight
-        # (bucket_split)
-        self.grad_ext = torch.zeros(off + 4, device=self.device, dtype=torch.float32)
-        self.grad = self.grad_ext[4:]
-        self.dp_flag = self.grad_ext[0:1]
-        # generation of `flat` for writers torch's version counter does not see (the device-side
-        # Adam of any trainer on this net, a raw-pointer kernel, a collective): every such write
-        # bumps it (params_changed()), and a trainer trusts its bf16 weight copies only while
-        # (generation, flat._version) is what it was when the copies were made (ADVICE r5)
-        self.generation = 0
-        self.reset_parameters(seed)
-
-    def params_changed(self):
-        """Declare that `flat` was rewritten by means that may bypass torch's version counter:
-        every trainer on this net re-derives its bf16 weight copies on its next step."""
-        self.generation += 1
-
-    def bucket_split(self):
-        """Index into grad_ext between the data-parallel buckets: [0, split) = the status flag and
-        every recurrent layer (complete after the last BPTT), [split, end) = the Linear, the speaker
-        embedding, ADDJUST and the 'align' attention weights (complete before the first BPTT)."""
-        return 4 + self.offsets["mix.Linear.weight"][0]
-
-    def bucket_mid(self, layer):
-        """Index into grad_ext where the recurrent layers >= ``layer`` start (layers are contiguous in
-        order): the three-bucket step's middle bucket is [bucket_mid(layer), bucket_split())."""
-        return 4 + self.offsets[f"mix.layer.weight_ih_l{layer}"][0]
-
-    def named_parameters(self):
-        return {name: self.view(name) for name, _ in self.specs}
-
-    def reset_parameters(self, seed=1):
-        """torch default initialisers (nn.LSTM/GRU, nn.Linear, nn.Embedding)."""
-        g = torch.Generator().manual_seed(seed)
-        for name, shape in self.specs:
-            if name.startswith("mix.layer."):
-                k = 1.0 / math.sqrt(self.H)
-                t = torch.empty(shape).uniform_(-k, k, generator=g)
-            elif name == "emb.layer.weight":
-                t = torch.randn(shape, generator=g)
-            elif name.endswith("bias"):
-                k = 1.0 / math.sqrt(2 * self.H)
-                t = torch.empty(shape).uniform_(-k, k, generator=g)
-            else:
-                k = 1.0 / math.sqrt(shape[1])
-                t = torch.empty(shape).uniform_(-k, k, generator=g)
-            self.view(name).copy_(t)
-
-
-class DiscNet(FlatParams):
-    """Parameters of the adversarial Discriminator (TDAA_beta/main_run_sstune_dis.py:318-336) for (T, F)
-    maps, flat fp32 under the reference's eight ``state_dict`` keys with the shapes of
-    ``compat.myNet.Discriminator`` (a ``_dislayer_`` file or that module's state_dict loads unchanged;
-    ``checkpoint.load_reference_discriminator`` / ``save_reference_discriminator`` take a DiscNet as their
-    module), and the two flat gradients of the adversarial step: ``grad_dis`` = d(L_dt + L_df) and
-    ``grad_adv`` = d(lambda L_adv) (SepTrainer(adversary=...))."""
-
-    def __init__(self, T, F=129, device="cuda", seed=1):
-        hw = (ctypes.c_int * 6)()
-        feat = _lib.query("dl4ss_disc_dims", int(T), int(F), hw)
-        if feat < 0:
-            raise ValueError(f"DiscNet: a ({T}, {F}) map is smaller than the 15 x 15 minimum")
-        self.T, self.F, self.hw, self.feat = int(T), int(F), list(hw), feat
-        self._allocate([("cnn.weight", (64, 1, 3, 3)), ("cnn.bias", (64,)), ("cnn1.weight", (64, 64, 3, 3)),
-                        ("cnn1.bias", (64,)), ("cnn2.weight", (64, 64, 3, 3)), ("cnn2.bias", (64,)),
-                        ("final.weight", (1, feat)), ("final.bias", (1,))], device)
-        self.grad_dis = torch.zeros_like(self.flat)
-        self.grad_adv = torch.zeros_like(self.flat)
-        self.reset_parameters(seed)
-
-    def load_state_dict(self, sd):
-        """The eight keys, each with this net's shape (a file saved at another map size raises)."""
-        for name, shape in self.specs:
-            if tuple(sd[name].shape) != tuple(shape):
-                raise ValueError(f"DiscNet: {name} has shape {tuple(sd[name].shape)}, expected {tuple(shape)}")
-        super().load_state_dict(sd)
-
-    def reset_parameters(self, seed=1):
-        """torch's default initialisers of nn.Conv2d / nn.Linear: uniform +-1/sqrt(fan_in), weight and bias."""
-        g = torch.Generator().manual_seed(seed)
-        fan = {"cnn": 9, "cnn1": 576, "cnn2": 576, "final": self.feat}
-        for name, shape in self.specs:
-            k = 1.0 / math.sqrt(fan[name.split(".")[0]])
-            self.view(name).copy_(torch.empty(shape).uniform_(-k, k, generator=g))
-
-
-# settled A/B knobs (DESIGN.md section 11 keeps their last figures): the default of each is the only path now
-RETIRED_KNOBS = ("DL4SS_DX_SPLIT", "DL4SS_DEFER_BIAS", "DL4SS_SIDE_LATE", "DL4SS_DW_SPLITS", "DL4SS_DW_CFG")
-
-
-def step_plan(net, batch, n_samples, precision, rnn_precision=None, process_group=None):
-    """Every schedule decision of a SepTrainer, derived once from its arguments, the recurrence's plan,
-    the CU count and the environment knobs -- each knob is read and validated here and nowhere else.
-    DESIGN.md section 11 has the table of knobs and the measurement behind every default.  The fields
-    of the result become the trainer's attributes of the same names."""
-    env = os.environ
-    for name in RETIRED_KNOBS:
-        if name in env:
-            raise ValueError(f"{name} is retired, its default is the only path (DESIGN.md section 11): unset it")
-    p = types.SimpleNamespace()
-    B, T, F, H, L = batch, ops.n_frames(n_samples), net.F, net.H, net.L
-    BT, FE, NGH = B * T, F * net.E, _ngate(net.cell) * H
-    # precision "bf16": every GEMM on the LDS-DMA MFMA kernel over bf16 operands; "bf16s": the forward GEMMs over
-    # split (hi + lo) operands, three terms; "bf16s2": two terms into the layers >= 1.  The recurrence (bf16 MFMA
-    # matvec, fp32 state) and the whole backward are the bf16 step's in all three (DESIGN.md section 6)
-    p.split = precision in ("bf16s", "bf16s2")
-    p.split_x2 = precision == "bf16s2"
-    # recurrent matvec precision (defaults to the GEMM precision): "fp32" exact VALU, "bf16" MFMA
-    p.rnn_precision = "bf16" if (p.split and rnn_precision in (None, precision)) else (rnn_precision or precision)
-    if p.split and p.rnn_precision != "bf16":
-        raise ValueError(f"precision '{precision}' runs the bf16 recurrence (rnn_precision bf16)")
-    p.fast = precision in ("bf16", "bf16s", "bf16s2") and p.rnn_precision == "bf16"
-    p.grouped = L <= 5  # <= 16 problems per grouped weight-gradient launch; deeper nets: a GEMM per gradient
-    # one hand-off workspace per (layer, pass), zeroed once: a completed launch leaves it fit for the next
-    # (T >= 4).  DL4SS_WS_FILL=1: a fill per step
-    p._ws_fill = T < 4 or env.get("DL4SS_WS_FILL", "0") == "1"
-    p.dh_split = int(env.get("DL4SS_DH_SPLIT", "3"))  # dH split-K
-    # input projections fused into the packed recurrence: "1" every layer, "l0" the first only, "0" none
-    xw = env.get("DL4SS_RNN_XW", "1")
-    if xw not in ("0", "1", "l0"):
-        raise ValueError(f"DL4SS_RNN_XW={xw}: expected 0, 1 or l0")
-    p.xw = p.fast and xw != "0" and not p.split
-    p.xw_kmax = 160 if xw == "l0" else 640
-    # bf16s: the first layer's split-operand projection (K' = 3 pad8(F) = 408 <= 640) is fused too
-    p.xw_split0 = p.split and xw != "0"
-    # data parallel: "2" the gradient leaves in two buckets around the grouped launch, "3" three (the upper
-    # layers >= dp_layer in the middle), "0" one flat all-reduce
-    nb = env.get("DL4SS_DP_BUCKETS", "2")
-    if nb not in ("0", "1", "2", "3"):
-        raise ValueError(f"DL4SS_DP_BUCKETS={nb}: expected 0, 1 (alias of 2), 2 or 3")
-    p.buckets = process_group is not None and p.fast and p.grouped and nb != "0"
-    p.dp_layer = L // 2 if (p.buckets and nb == "3" and L >= 2) else None
-    # grouped bf16 backward: every gradient has exactly one writer (beta 0), so no zeroing pass over the
-    # flat gradient.  DL4SS_GRAD_ZERO=1 restores it
-    p.zero_free = p.fast and p.grouped and env.get("DL4SS_GRAD_ZERO", "0") != "1"
-    p._gbeta = 0.0 if p.zero_free else 1.0
-    # Adam writes the bf16 weight copies itself.  DL4SS_ADAM_SHADOW=0: a conversion launch every step
-    p._shadow_on = p.fast and env.get("DL4SS_ADAM_SHADOW", "1") != "0"
-    cuda = net.device.type == "cuda"
-    rnn = ops.birnn_plan(net.cell, B, H) if (p.fast and cuda) else None
-    # dW_lin (+ the Linear's bias gradient as row sums) on a side stream beside the BPTT chain, one persistent
-    # workgroup per CU the recurrence leaves free, when a cost model says it fits inside the chain.
-    # DL4SS_SIDE_DWLIN: "0" off, "1" on, "grid,cfg,split[,one_per_cu]" a forced shape
-    p.side = None
-    side = env.get("DL4SS_SIDE_DWLIN", "")
-    if p.fast and p.grouped and side != "0" and cuda:
-        if side and side != "1":
-            v = [int(x) for x in side.split(",")]
-            p.side = (v[0], v[1], v[2], bool(v[3]) if len(v) > 3 else True)
-        else:
-            cus = torch.cuda.get_device_properties(net.device).multi_processor_count
-            free = cus - (rnn["grid"] if rnn else 1 << 30)
-            flops = 2.0 * FE * (2 * H) * BT
-            if free >= 8 and (flops / (free * 2.75e12) < L * T * 1.75e-6 * 0.85 or side == "1"):
-                p.side = (free, 2, 1, False)
-    # the top layer's BPTT sums the dH GEMM's split-K slabs as it loads dOut (no combine launch): three slabs
-    # and batch chunks of 4 only, the instance that measured no slower.  DL4SS_DH_SLABS=0: the combine launch
-    p.dh_slabs = 1
-    if p.fast and env.get("DL4SS_DH_SLABS", "1") != "0" and rnn is not None and rnn["BC"] == 4:
-        nsl = _lib.query("dl4ss_gemm_bf16_gl_ws_bytes", BT, 2 * H, FE, max(1, p.dh_split), 1) // (BT * 2 * H * 4)
-        p.dh_slabs = 3 if nsl == 3 else 1
-
-    # split-K of the grouped weight-gradient launch (dW_lin, dW_ih, dW_hh): dW_ih goes unsplit when the group
-    # fills >= 3 waves of the 512 workgroup slots without it (C2: 1793 workgroups; the BiGRU-2L nets: 999)
-    def tiles(m, n):
-        return ((m + 127) // 128) * ((n + 127) // 128)
-
-    wg1 = 2 * tiles(FE, 2 * H) + sum(tiles(2 * NGH, F if l == 0 else 2 * H) for l in range(L)) + \
-        4 * 2 * L * tiles(NGH, H)
-    p.dw_splits = (2, 1 if wg1 >= 3 * 512 else 2, 4)
-    return p
+from .params import DiscNet, FlatParams, SepNet, _ngate  # noqa: F401 (re-exported)
+from .plan import RETIRED_KNOBS, check_args, step_plan  # noqa: F401 (re-exported)
+from .voiceprint import VoiceprintStep
 
 
 class SepTrainer:
@@ -295,58 +42,18 @@ class SepTrainer:
     trains with the mask net (its own guarded Adam at ``voiceprint_lr``, default ``lr``) and the memory rows of
     the batch's speakers are rewritten after every applied update: ``memory_refresh`` "reference" re-encodes
     with the updated weights first (nnet.py:131-135), "reuse" stores the step's own queries.  fp32, mode
-    "label", single GPU, eager only; everything else is refused (_vp_refuse).  None (the default): no launch is
+    "label", single GPU, eager only; everything else is refused (plan.check_args).  None (the default): no launch is
     added and no line of the step changes."""
 
     def __init__(self, net, batch, k, n_samples, mode="label", precision="fp32", lr=2e-4, sum_weight=0.5,
                  loss_channels=None, betas=(0.9, 0.999), eps=1e-8, process_group=None, rnn_precision=None,
                  adversary=None, adv_weight=1.0, adv_lr=None, disc_adv_update=True, clip_norm=None,
                  adv_clip_norm=None, voiceprint=None, memory=None, voiceprint_lr=None, memory_refresh="reference"):
-        if mode not in ("label", "pit", "crm"):
-            raise ValueError(mode)
-        if voiceprint is not None or memory is not None:  # refused here, before any device call
-            self._vp_refuse(net, batch, k, mode, precision, loss_channels, process_group, adversary, clip_norm,
-                            voiceprint, memory, memory_refresh)
-        self.vnet, self.memory, self.memory_refresh = voiceprint, memory, memory_refresh
-        # gradient clipping (_clip_setup): thresholds checked here, before any device call
-        self.clip_norm = None if clip_norm is None else ops.check_clip_norm(clip_norm)
-        self.adv_clip_norm = None if adv_clip_norm is None else ops.check_clip_norm(adv_clip_norm, "adv_clip_norm")
-        if adv_clip_norm is not None and adversary is None:
-            raise ValueError("adv_clip_norm needs an adversary")
-        if (mode == "crm") != net.crm:
-            raise ValueError("cRM mode needs a cRM net (query width 2E) and vice versa")
+        self.clip_norm, self.adv_clip_norm = check_args(  # every refusal, before any device call
+            net, batch, k, n_samples, mode, precision, rnn_precision, loss_channels, process_group, adversary,
+            clip_norm, adv_clip_norm, voiceprint, memory, memory_refresh)
+        self.vnet, self.memory, self.memory_refresh, self.adversary = voiceprint, memory, memory_refresh, adversary
         self.align = getattr(net, "attention", "dot") == "align"
-        if adversary is not None:  # the adversarial step (_adv_setup): refused here, before any device call
-            T_ = ops.n_frames(n_samples)
-            if not isinstance(adversary, DiscNet):
-                raise ValueError("adversary: expected an engine.DiscNet")
-            if mode == "crm":
-                raise ValueError("adversary: the adversarial term is built for the magnitude modes, not 'crm'")
-            if loss_channels:
-                raise ValueError("adversary: loss_channels is unsupported with an adversary")
-            if self.align:
-                raise ValueError("adversary: attention='align' is unsupported with an adversary")
-            if process_group is not None:
-                raise ValueError("adversary: no data-parallel adversarial step (the Discriminator's gradients are "
-                                 "not all-reduced)")
-            if T_ < 15:
-                raise ValueError(f"adversary: {T_} frames, the Discriminator needs maps of at least 15 x 15")
-            if (adversary.T, adversary.F) != (T_, net.F):
-                raise ValueError(f"adversary: a DiscNet for ({adversary.T}, {adversary.F}) maps, this trainer's "
-                                 f"are ({T_}, {net.F})")
-            if (adversary.device.type, adversary.device.index or 0) != (net.device.type, net.device.index or 0):
-                raise ValueError("adversary: the DiscNet lives on another device than the net")
-        self.adversary = adversary
-        if self.align:
-            if mode == "crm":
-                raise ValueError("attention='align' supports the modes 'label' and 'pit', not 'crm'")
-            if loss_channels:
-                raise ValueError("attention='align' does not support loss_channels")
-            if precision in ("bf16s", "bf16s2") or (precision == "bf16" and (rnn_precision or precision) == "bf16"):
-                raise ValueError(f"attention='align' is not built for the bf16 / bf16s fast paths "
-                                 f"(precision={precision!r}, rnn_precision={rnn_precision!r}); use precision='fp32'")
-            if net.E != 50:
-                raise ValueError("attention='align' is built for embedding size 50")
         # rnn_precision, fast, split, split_x2, grouped, _ws_fill, dh_split, dh_slabs, xw, xw_kmax, xw_split0, buckets,
         # dp_layer, side, dw_splits, zero_free, _gbeta, _shadow_on
         vars(self).update(vars(step_plan(net, batch, n_samples, precision, rnn_precision, process_group)))
@@ -356,10 +63,7 @@ class SepTrainer:
         # varies from launch to launch).  The 'align' step keeps every GEMM in one piece instead, so that its
         # gradients are bitwise reproducible, eager or replayed
         self._sk = 1 if self.align else "auto"
-        self.lr, self.betas, self.eps = lr, betas, eps
         self.pg = process_group
-        from . import dp
-
         # data parallel: the gradient is all-reduced with SUM and Adam applies 1 / world
         self.world = dp.world(process_group) if process_group is not None else 1
         self.T = ops.n_frames(n_samples)
@@ -419,9 +123,10 @@ class SepTrainer:
         # {hand-off timed out, refused-update count} (the recurrence kernels set [0]; the guarded
         # Adam counts its refusals in [1])
         self.status = torch.zeros(2, device=dev, dtype=torch.int32)
-        self.m = torch.zeros_like(net.flat)
-        self.v = torch.zeros_like(net.flat)
-        self.step_count = 0
+        self.opt = adam.GuardedAdam(net.flat, self.status, self.loss, lr, betas, eps, clip_norm=self.clip_norm)
+        self.m, self.v = self.opt.m, self.opt.v
+        if self.clip_norm is not None:
+            self.grad_norm, self._nonfinite = self.opt.grad_norm, self.opt.nonfinite  # (_nonfinite: the tests read it)
         nch = loss_channels if loss_channels else K
         self.s1 = 1.0 / (B * nch * T * F)
         self.s2 = 0.0 if (mode == "crm" or loss_channels) else sum_weight / (B * T * F)
@@ -430,11 +135,20 @@ class SepTrainer:
         self._in_chain = False
         self._side_stream = self._side_gemm = self._fork_ev = None
         self._wb_ver = None
+        self.adv = self.adv_opt = self.vp = None
         if adversary is not None:
-            self._adv_setup(adv_weight, adv_lr, disc_adv_update)
-        self._clip_setup()
+            self.adv = AdvStep(adversary, B, K, self._mag, precision, self.status, self.loss,
+                               lr if adv_lr is None else adv_lr, betas, eps, adv_weight, disc_adv_update,
+                               self.adv_clip_norm)
+            a = self.adv  # the documented names, and the two private ones the tests read (_dmaps, _dy)
+            self.adv_opt, self.adv_m, self.adv_v, self.adv_weight = a.opt, a.opt.m, a.opt.v, a.adv_weight
+            self.adv_loss, self.adv_scores, self.gext, self._dmaps, self._dy = a.adv_loss, a.scores, a.gext, a.maps, a.y
+            if self.adv_clip_norm is not None:
+                self.adv_grad_norm = self.adv_opt.grad_norm  # [grad_dis | grad_adv]
         if voiceprint is not None:
-            self._vp_setup(voiceprint_lr)
+            self.vp = VoiceprintStep(voiceprint, memory, memory_refresh, self.mag_src, self.spk, self.q, self.dq,
+                                     self.status, self.loss, lr if voiceprint_lr is None else voiceprint_lr, betas, eps)
+            self.vp_enc, self.vp_opt = self.vp.enc, self.vp.opt
         if not self.fast:
             return
         # the bf16 step's operands, each produced directly as bf16 by the kernel that forms it (the BiRNN
@@ -481,6 +195,12 @@ class SepTrainer:
         if net.cell == "lstm":  # the LSTM BPTT never reads the fp32 h_{t-1}
             self.hprev = [None] * net.L
 
+    # the documented scalars live in the optimizers, read / write (a schedule assigns lr, tests restore the counts)
+    lr, adv_lr, vp_lr = (adam.delegate(o, "lr") for o in ("opt", "adv_opt", "vp_opt"))
+    step_count = adam.delegate("opt", "step_count")
+    skipped_nonfinite = adam.delegate("opt", "skipped_nonfinite")
+    adv_step_count = adam.delegate("adv_opt", "step_count")
+    adv_skipped_nonfinite = adam.delegate("adv_opt", "skipped_nonfinite", default=0)
 
     # ------------------------------------------------------------------ features
     def features(self, raw, gains, lengths=None):
@@ -634,8 +354,8 @@ class SepTrainer:
         else:
             ops.gemm(xin, w, transB=True, bias=net.view("mix.Linear.bias"), epilogue=ops.EPI_TANH, out=self.V,
                      precision=self.precision)
-        if self.vnet is not None:  # the queries are voiceprints read back from the speaker memory
-            self._vp_queries(self.q)
+        if self.vp is not None:  # the queries are voiceprints read back from the speaker memory
+            self.vp.queries(self.q)
             return
         wadj = net.view("adj.layer.weight") if net.adjust else None
         # (bf16: the time mean is already in self.mean, the query kernel reads no layer output)
@@ -691,15 +411,15 @@ class SepTrainer:
         """Fused attention + loss + dPre (in place over V) + dq; returns loss (device)."""
         st = _lib.stream_ptr()
         perm = None
-        adv = self.adversary is not None
+        adv = self.adv is not None
         if self.mode == "pit" or adv:  # (an adversary in label order: a COST pass only for the predictions)
-            self.attn(0, pred_out=self.pred if adv else None)
+            self.attn(0, pred_out=self.adv.pred if adv else None)
         if self.mode == "pit":
             _lib.call("dl4ss_pit_select", _lib.ptr(self.part_loss), self.B, self.K, self.nblk, _lib.ptr(self.perm), st)
             perm = self.perm
         if adv:  # the Discriminator on [true; predicted], its two gradients and gext = d(lambda L_adv)/dpred
-            self._adv_disc()
-        self.attn(1, perm, gext=self.gext if adv else None)
+            self.adv.disc_grads()
+        self.attn(1, perm, gext=self.adv.gext if adv else None)
         if self.align:
             # the loss from the same partials; dq and the three attention-weight gradients from the align
             # partials, straight into their views of the flat gradient (backward_early zeroes only the
@@ -715,116 +435,6 @@ class SepTrainer:
         _lib.call("dl4ss_loss_finalize", _lib.ptr(self.part_loss), self.B, self.K, self.nblk, _lib.ptr(perm),
                   self.s1, self.s2, _lib.ptr(self.loss), _lib.ptr(self.part_dq), self.net.W, _lib.ptr(self.dq), st)
         return self.loss
-
-    # ------------------------------------------------------------------ adversarial term
-    def _adv_setup(self, adv_weight, adv_lr, disc_adv_update):
-        """Buffers of the adversarial step (TDAA_beta/main_run_sstune_dis.py:613-647 with detach_fake, the
-        adversarial term weighted by ``adv_weight``): the Discriminator's activations over the 2 B K maps
-        [true; predicted], their gradients, the scores and loss heads, gext, the split-K workspace and the
-        Discriminator's Adam state.  It runs in fp32 for precision 'fp32', in the bf16 activation mode
-        otherwise."""
-        D, B, K, T, F = self.adversary, self.B, self.K, self.T, self.F
-        dev, N = self.net.device, self.B * self.K
-        self.adv_weight = float(adv_weight)
-        self.adv_lr = self.lr if adv_lr is None else adv_lr
-        self.disc_adv_update = bool(disc_adv_update)
-        self._dprec = ops.PREC["fp32" if self.precision == "fp32" else "bf16"]
-        dt = torch.float32 if self._dprec == 0 else torch.bfloat16
-        f32 = dict(device=dev, dtype=torch.float32)
-        self.pred = self._mag[B + N:].view(B, K, T, F)  # mask |X|, written by the COST pass (pred_out)
-        self._dmaps = self._mag[B:]  # (2 B K, T, F): the sources' magnitudes, then the predictions
-        self._dy = [torch.empty(2 * N, D.hw[2 * l], D.hw[2 * l + 1], 64, device=dev, dtype=dt) for l in range(3)]
-        self._ddy = [torch.empty_like(y) for y in self._dy]
-        self.adv_scores = torch.empty(2 * N, **f32)
-        self._dlogit = torch.empty(2 * N, **f32)
-        self._ddz = torch.empty(2 * N, **f32)
-        self._ds_dis = torch.empty(2 * N, **f32)
-        self._ds_adv = torch.empty(N, **f32)
-        self.adv_loss = torch.zeros(3, **f32)  # [L_dt, L_df, L_adv] (L_adv unweighted)
-        self.gext = torch.empty(B, K, T, F, **f32)
-        self._dws_bytes = _lib.query("dl4ss_disc_ws_bytes", 2 * N, T, F)
-        if self._dws_bytes < 0:
-            raise RuntimeError(f"Discriminator shape unsupported (N={2 * N}, T={T}, F={F})")
-        self._dws = torch.empty((self._dws_bytes + 3) // 4, **f32)
-        self.adv_m = torch.zeros_like(D.flat)
-        self.adv_v = torch.zeros_like(D.flat)
-        self.adv_step_count = 0
-
-    def _adv_disc(self):
-        """Scores of the 2 B K maps (one forward), the loss heads, then two backwards: all maps without the
-        input gradient -> grad_dis = d(L_dt + L_df), the predicted maps with conv1's dX -> grad_adv =
-        d(lambda L_adv) and gext = d(lambda L_adv)/dpred.  All on the current stream, at the pre-step weights."""
-        D, N, T, F, p, st = self.adversary, self.B * self.K, self.T, self.F, self._dprec, _lib.stream_ptr()
-        hw = D.hw
-        w = lambda name: _lib.ptr(D.view(name))  # noqa: E731
-        y1, y2, y3 = self._dy
-        _lib.call("dl4ss_disc_conv1_fwd", p, _lib.ptr(self._dmaps), w("cnn.weight"), w("cnn.bias"), 2 * N, T, F,
-                  _lib.ptr(y1), st)
-        _lib.call("dl4ss_disc_conv64_fwd", p, _lib.ptr(y1), w("cnn1.weight"), w("cnn1.bias"), 2 * N, hw[0], hw[1],
-                  _lib.ptr(y2), st)
-        _lib.call("dl4ss_disc_conv64_fwd", p, _lib.ptr(y2), w("cnn2.weight"), w("cnn2.bias"), 2 * N, hw[2], hw[3],
-                  _lib.ptr(y3), st)
-        _lib.call("dl4ss_disc_head_fwd", p, _lib.ptr(y3), w("final.weight"), w("final.bias"), 2 * N, hw[4], hw[5],
-                  _lib.ptr(self._dlogit), _lib.ptr(self.adv_scores), st)
-        _lib.call("dl4ss_disc_adv_heads", _lib.ptr(self.adv_scores), N, self.adv_weight, _lib.ptr(self.adv_loss),
-                  _lib.ptr(self._ds_dis), _lib.ptr(self._ds_adv), st)
-        self._adv_disc_bwd(0, 2 * N, self._ds_dis, D.grad_dis, None)
-        self._adv_disc_bwd(N, N, self._ds_adv, D.grad_adv, self.gext)
-
-    def _adv_disc_bwd(self, first, n, dscore, g, dx):
-        """The Discriminator's backward over the maps [first, first + n) from their dscore into the flat
-        gradient ``g``; ``dx`` (n, T, F): the input gradient too."""
-        D, T, F, p, st = self.adversary, self.T, self.F, self._dprec, _lib.stream_ptr()
-        hw = D.hw
-        w = lambda name: _lib.ptr(D.view(name))  # noqa: E731
-        gr = lambda name: _lib.ptr(D.view(name, g))  # noqa: E731
-        y1, y2, y3 = (y[first:first + n] for y in self._dy)
-        d1, d2, d3 = (d[:n] for d in self._ddy)
-        ws, wsn = _lib.ptr(self._dws), self._dws_bytes
-        _lib.call("dl4ss_disc_head_bwd", p, _lib.ptr(y3), w("final.weight"), _lib.ptr(self.adv_scores[first:first + n]),
-                  _lib.ptr(dscore), 0.0, n, hw[4], hw[5], None, _lib.ptr(self._ddz), gr("final.weight"),
-                  gr("final.bias"), _lib.ptr(d3), st)
-        _lib.call("dl4ss_disc_conv64_bwd", p, _lib.ptr(y2), _lib.ptr(y3), _lib.ptr(d3), w("cnn2.weight"), n, hw[2],
-                  hw[3], _lib.ptr(d2), gr("cnn2.weight"), gr("cnn2.bias"), ws, wsn, st)
-        _lib.call("dl4ss_disc_conv64_bwd", p, _lib.ptr(y1), _lib.ptr(y2), _lib.ptr(d2), w("cnn1.weight"), n, hw[0],
-                  hw[1], _lib.ptr(d1), gr("cnn1.weight"), gr("cnn1.bias"), ws, wsn, st)
-        _lib.call("dl4ss_disc_conv1_bwd", p, _lib.ptr(self._dmaps[first:first + n]), _lib.ptr(y1), _lib.ptr(d1),
-                  w("cnn.weight"), n, T, F, _lib.ptr(dx), gr("cnn.weight"), gr("cnn.bias"), ws, wsn, st)
-
-    def _clip_setup(self):
-        """Buffers of the global-norm clip (clip_norm / adv_clip_norm): the fp64 partials of the gradient's sum
-        of squares, {norm before clipping, coefficient} as the clipped Adam leaves them on the device, and the
-        device counters of the updates refused for a non-finite gradient."""
-        dev = self.net.device
-        self.skipped_nonfinite = 0      # refused for a non-finite gradient, as check() has counted them
-        self.adv_skipped_nonfinite = 0  # the same for the Discriminator's updates
-        if self.clip_norm is not None:
-            self._clip_part = torch.zeros(ops.grad_sumsq_parts(self.net.grad.numel()), device=dev,
-                                          dtype=torch.float64)
-            self.grad_norm = torch.zeros(2, device=dev, dtype=torch.float32)
-            self._nonfinite = torch.zeros(1, device=dev, dtype=torch.int32)
-        if self.adv_clip_norm is not None:
-            self._adv_clip_part = torch.zeros(ops.grad_sumsq_parts(self.adversary.numel), device=dev,
-                                              dtype=torch.float64)
-            self.adv_grad_norm = torch.zeros(2, 2, device=dev, dtype=torch.float32)  # [grad_dis | grad_adv]
-            self._adv_nonfinite = torch.zeros(1, device=dev, dtype=torch.int32)
-
-    def _adv_optimizer_step(self):
-        """The Discriminator's updates, in the reference's order (dis.py:627-628, 646-647: one optimizer over
-        both nets): Adam on grad_dis, then (disc_adv_update) Adam on grad_adv -- each a step of its own Adam
-        state, guarded by the same status word as the separation net's."""
-        D = self.adversary
-        for i, g in enumerate((D.grad_dis, D.grad_adv) if self.disc_adv_update else (D.grad_dis,)):
-            self.adv_step_count += 1
-            if self.adv_clip_norm is not None:  # each update clipped on its own gradient
-                ops.grad_sumsq(g, self._adv_clip_part)
-                ops.adam_(D.flat, g, self.adv_m, self.adv_v, self.adv_step_count, self.adv_lr, self.betas, self.eps,
-                          status=self.status, loss=self.loss,
-                          clip=(self._adv_clip_part, self.adv_clip_norm, self.adv_grad_norm[i], self._adv_nonfinite))
-                continue
-            _lib.call("dl4ss_adam_guarded", _lib.ptr(D.flat), _lib.ptr(g), _lib.ptr(self.adv_m), _lib.ptr(self.adv_v),
-                      D.numel, float(self.adv_lr), float(self.betas[0]), float(self.betas[1]), float(self.eps),
-                      self.adv_step_count, _lib.ptr(self.status), _lib.ptr(self.loss), _lib.stream_ptr())
 
     # ------------------------------------------------------------------ backward
     def _weight_grad_group(self):
@@ -933,7 +543,7 @@ class SepTrainer:
 
     def _backward_chain(self):
         """The bf16 BPTT / dX chain down the layers, the side stream joined at its end.  No collective may
-        start while it is being enqueued (_no_collective_in_chain)."""
+        start while it is being enqueued (_allreduce)."""
         self._in_chain = True
         try:
             self._enqueue_chain()
@@ -1041,12 +651,8 @@ class SepTrainer:
         last layer's output gradient."""
         net, B, T, H = self.net, self.B, self.T, self.net.H
         g = net.grad
-        if self.vnet is not None:
-            # dq -> the voiceprints' gradient through the memory, then the encoder's BPTT into vnet.grad (every
-            # element written); emb.layer.weight's gradient stays zero (backward_early zeroed it)
-            ops.spk_memory_bwd(self.dq.view(B * self.K, -1), self.vp_enc.vec, self.vp_u, self.spk.view(-1),
-                               self.memory.mem, dv=self.vp_dv)
-            self.vp_enc.backward(self.vp_dv)
+        if self.vp is not None:  # emb.layer.weight's gradient stays zero (backward_early zeroed it)
+            self.vp.backward()
             return
         wadj = net.view("adj.layer.weight") if net.adjust else None
         _lib.call("dl4ss_query_bwd_ex", _lib.ptr(self.dq), B, T, 2 * H, _lib.ptr(self.spk),
@@ -1099,60 +705,43 @@ class SepTrainer:
             _lib.call("dl4ss_status_flag", _lib.ptr(self.status), _lib.ptr(self.net.dp_flag), _lib.stream_ptr())
 
     def allreduce(self):
-        """START the RCCL all-reduce (SUM) of the whole flat gradient, asynchronously; Adam applies
-        the 1 / world of the mean (no separate pass over the buffer).  The slot in front of the
-        gradient carries this rank's hand-off status flag (dl4ss_status_flag, written at the end of
-        backward()): after the sum it is non-zero on every rank iff a hand-off timed out on any
-        rank, and the guarded Adam reads it (a timed-out rank's incomplete gradient must
-        not reach the healthy ranks' weights either).  Bucketed steps (self.buckets) use
+        """START the RCCL all-reduce (SUM) of the whole flat gradient, asynchronously; Adam applies the 1 / world of
+        the mean (no separate pass over the buffer).  The slot in front of the gradient carries this rank's hand-off
+        status flag (dl4ss_status_flag, written at the end of backward()): after the sum it is non-zero on every
+        rank iff a hand-off timed out on any rank, and the guarded Adam reads it (a timed-out rank's
+        incomplete gradient must not reach the healthy ranks' weights either).  Bucketed steps (self.buckets) use
         allreduce_early / _late.
 
         Contract: net.grad is complete only after wait_allreduce() (optimizer_step()
         calls it), and it then holds the SUM over ranks, not the mean -- grad_mean() is the mean."""
-        if self.pg is None:
-            return
-        from . import dp
+        if self.pg is not None:
+            self._allreduce(None, None)
 
-        self._no_collective_in_chain()
-        self._works.append(dp.allreduce_sum_async(self.net.grad_ext, self.pg))
-
-    def _no_collective_in_chain(self):
-        """Invariant: no collective starts while the BPTT chain is being enqueued.  The
-        persistent recurrence needs all its workgroups co-resident, and the side-stream dW_lin holds
-        every CU the recurrence plan leaves free for the whole chain; a collective kernel placed
-        beside the chain could keep a recurrence workgroup off the device (a hand-off timeout, then a
+    def _allreduce(self, lo, hi):
+        """Start the asynchronous SUM all-reduce of net.grad_ext[lo:hi].  Invariant: no collective starts
+        while the BPTT chain is being enqueued.  The persistent recurrence needs all its workgroups co-resident, and
+        the side-stream dW_lin holds every CU the recurrence plan leaves free for the whole chain; a collective
+        kernel placed beside the chain could keep a recurrence workgroup off the device (a hand-off timeout, then a
         refused step).  Every all-reduce of the step therefore starts after the chain."""
         if self._in_chain:
             raise RuntimeError("a gradient all-reduce was started inside the BPTT chain")
+        self._works.append(dp.allreduce_sum_async(self.net.grad_ext[lo:hi], self.pg))
 
     def allreduce_early(self):
-        """Start the SUM all-reduce of the early bucket (Linear -- formed on the side stream, joined at the
-        end of the chain --, embedding, ADDJUST gradients): asynchronous, on the process group's stream
-        after the work enqueued so far.  The bucketed step starts it after the BPTT chain, beside the
-        recurrent layers' weight-gradient launch."""
-        from . import dp
-
-        self._no_collective_in_chain()
-        self._works.append(dp.allreduce_sum_async(self.net.grad_ext[self.net.bucket_split():], self.pg))
+        """Start the SUM all-reduce of the early bucket (Linear -- formed on the side stream, joined at the end of the
+        chain --, embedding, ADDJUST gradients): asynchronous, on the process group's stream after the work enqueued
+        so far.  The bucketed step starts it after the BPTT chain, beside the recurrent layers' weight gradients."""
+        self._allreduce(self.net.bucket_split(), None)
 
     def allreduce_mid(self):
         """Three buckets: start the SUM all-reduce of the upper recurrent layers (>= dp_layer), complete
         after the first weight-gradient launch, beside the second."""
-        from . import dp
-
-        self._no_collective_in_chain()
-        net = self.net
-        self._works.append(dp.allreduce_sum_async(net.grad_ext[net.bucket_mid(self.dp_layer):net.bucket_split()],
-                                                  self.pg))
+        self._allreduce(self.net.bucket_mid(self.dp_layer), self.net.bucket_split())
 
     def allreduce_late(self):
         """Start the SUM all-reduce of the late bucket: the status flag and every recurrent layer (two
         buckets), or the layers below dp_layer (three)."""
-        from . import dp
-
-        self._no_collective_in_chain()
-        end = self.net.bucket_mid(self.dp_layer) if self.dp_layer is not None else self.net.bucket_split()
-        self._works.append(dp.allreduce_sum_async(self.net.grad_ext[:end], self.pg))
+        self._allreduce(None, self.net.bucket_split() if self.dp_layer is None else self.net.bucket_mid(self.dp_layer))
 
     def wait_allreduce(self):
         """The current stream waits for every all-reduce started this step: net.grad then holds the
@@ -1188,110 +777,18 @@ class SepTrainer:
         Discriminator's updates run first and are guarded by adv_clip_norm alone: a non-finite separation
         gradient does not undo them."""
         self.wait_allreduce()
-        if self.adversary is not None:  # the Discriminator's updates first (the reference's order)
-            self._adv_optimizer_step()
-        self.step_count += 1
+        if self.adv is not None:  # the Discriminator's updates first (the reference's order)
+            self.adv.optimizer_step()
         shadow = self._shadow if (self._shadow_on and hasattr(self, "_shadow")) else None
-        clip = None
-        if self.clip_norm is not None:
-            ops.grad_sumsq(self.net.grad, self._clip_part)
-            clip = (self._clip_part, self.clip_norm, self.grad_norm, self._nonfinite)
-        ops.adam_(self.net.flat, self.net.grad, self.m, self.v, self.step_count, self.lr, self.betas, self.eps,
-                  status=self.status, loss=self.loss, dp_flag=self.net.dp_flag, gscale=1.0 / self.world,
-                  shadow=shadow, clip=clip)
+        self.opt.step(self.net.grad, dp_flag=self.net.dp_flag, gscale=1.0 / self.world, shadow=shadow)
         # the update bypasses torch's version counter: a new generation of the parameters, whose bf16
         # copies only this trainer holds (written by the same launch), and only if they were current
         # before it -- copies stale before the update stay stale after it
         fresh = shadow is not None and not self._wb_stale()
         self.net.params_changed()
         self._wb_ver = self._wb_key() if fresh else None
-        if self.vnet is not None:
-            self._vp_optimizer_step()
-
-    # ------------------------------------------------------------------ voiceprint queries
-    @staticmethod
-    def _vp_refuse(net, batch, k, mode, precision, loss_channels, process_group, adversary, clip_norm, vnet, memory,
-                   memory_refresh):
-        """Everything the voiceprint step is not built for, each with its reason (host checks only)."""
-        from .voiceprint import SpeakerMemory, VoiceprintNet
-
-        if vnet is None:
-            raise ValueError("memory: a SpeakerMemory needs voiceprint= (the encoder whose vectors it accumulates)")
-        if memory is None:
-            raise ValueError("voiceprint: the encoder needs memory= (a voiceprint.SpeakerMemory)")
-        if not isinstance(vnet, VoiceprintNet):
-            raise ValueError("voiceprint: expected a voiceprint.VoiceprintNet")
-        if not isinstance(memory, SpeakerMemory):
-            raise ValueError("memory: expected a voiceprint.SpeakerMemory")
-        if mode != "label":
-            raise ValueError(f"voiceprint: mode {mode!r} is unsupported, the enrolled query belongs to its own "
-                             "source (mode 'label')")
-        if net.crm:
-            raise ValueError("voiceprint: a cRM net (query width 2E) is unsupported")
-        if net.adjust:
-            raise ValueError("voiceprint: net.adjust is unsupported (ADDJUST adds to an embedding row, not to a "
-                             "memory row); build the SepNet with adjust=False")
-        if net.E != vnet.E:
-            raise ValueError(f"voiceprint: the encoder's vectors have {vnet.E} elements, the net's queries {net.E}")
-        if memory.E != vnet.E:
-            raise ValueError(f"memory: rows of {memory.E} elements, the encoder's vectors have {vnet.E}")
-        if net.F != vnet.F:
-            raise ValueError(f"voiceprint: the encoder reads {vnet.F} bins, the step's magnitudes have {net.F}")
-        if precision != "fp32":
-            raise ValueError(f"voiceprint: precision {precision!r} is unsupported, the voiceprint path is fp32")
-        if loss_channels:
-            raise ValueError("voiceprint: loss_channels is unsupported")
-        if adversary is not None:
-            raise ValueError("voiceprint: an adversary is unsupported")
-        if process_group is not None:
-            raise ValueError("voiceprint: no data-parallel voiceprint step (process_group; the encoder's gradient "
-                             "and the memory are not all-reduced)")
-        if clip_norm is not None:
-            raise ValueError("voiceprint: clip_norm is unsupported (one global norm over the two flat gradients "
-                             "needs a kernel change)")
-        if memory_refresh not in ("reference", "reuse"):
-            raise ValueError(f"memory_refresh {memory_refresh!r}: expected 'reference' or 'reuse'")
-        if batch * k > 1024:
-            raise ValueError(f"voiceprint: {batch * k} sources per step, the memory kernels take at most 1024")
-        dev = (net.device.type, net.device.index or 0)
-        for what, d in (("voiceprint", vnet.device), ("memory", memory.device)):
-            if (d.type, d.index or 0) != dev:
-                raise ValueError(f"{what}: lives on another device than the net")
-
-    def _vp_setup(self, voiceprint_lr):
-        from .voiceprint import VoiceprintEncoder
-
-        BK, E = self.B * self.K, self.vnet.E
-        f32 = dict(device=self.net.device, dtype=torch.float32)
-        self.vp_lr = self.lr if voiceprint_lr is None else voiceprint_lr
-        # the encoder over the step's B K clean magnitude maps; its recurrences share the step's status word
-        self.vp_enc = VoiceprintEncoder(self.vnet, BK, self.T, status=self.status)
-        self.vp_u = torch.empty(BK, E, **f32)
-        self.vp_dv = torch.empty(BK, E, **f32)
-        self.vp_q2 = torch.empty(BK, E, **f32)  # the refreshed rows ("reference")
-        self.vp_m = torch.zeros_like(self.vnet.flat)
-        self.vp_v = torch.zeros_like(self.vnet.flat)
-
-    def _vp_queries(self, q):
-        """q (B, K, E) = the memory rows of the step's speakers with this batch's unit voiceprints accumulated:
-        the masked encoder over the clean magnitudes the step's STFT wrote (silent frames, e.g. the zero tail of
-        a short source, are masked: rule 'nonzero'), then the memory forward.  (The STFT transforms frames in
-        pairs: a silent frame that shares its transform with a voiced one -- the first silent frame behind an odd
-        number of voiced ones -- carries that neighbour's rounding residue, ~1e-8 of it, and counts as valid.)"""
-        BK = self.B * self.K
-        vec = self.vp_enc.forward(self.mag_src.view(BK, self.T, self.F))
-        ops.spk_memory_fwd(vec, self.spk.view(-1), self.memory.mem, u=self.vp_u, q=q.view(BK, -1))
-
-    def _vp_optimizer_step(self):
-        """The encoder's guarded Adam (the same step count and status word: refused with the net's), then the
-        memory refresh, skipped on device when the update was refused."""
-        ops.adam_(self.vnet.flat, self.vnet.grad, self.vp_m, self.vp_v, self.step_count, self.vp_lr, self.betas,
-                  self.eps, status=self.status, loss=self.loss)
-        q = self.q
-        if self.memory_refresh == "reference":  # predict after train_on_batch (nnet.py:131-135)
-            q = self.vp_q2
-            self._vp_queries(q)
-        ops.spk_memory_store(q.view(self.B * self.K, -1), self.spk.view(-1), self.memory.mem, status=self.status)
+        if self.vp is not None:  # the encoder steps with the net's count, then the memory refresh
+            self.vp.optimizer_step(self.opt.step_count)
 
     def step(self, raw, gains, spk_idx, lengths=None):
         """One full training step on device-resident inputs; returns the loss tensor (not synced).  lengths (B, K)
@@ -1425,29 +922,15 @@ class SepTrainer:
         s, refused = (int(x) for x in self.status.tolist())
         if s or refused:
             self.status.zero_()
-            nf = nf_adv = 0
-            if self.clip_norm is not None:
-                nf = int(self._nonfinite.item())
-                self._nonfinite.zero_()
-            n_disc = (2 if self.disc_adv_update else 1) if self.adversary is not None else 0
-            if self.adv_clip_norm is not None:
-                nf_adv = int(self._adv_nonfinite.item())
-                self._adv_nonfinite.zero_()
-            # status[1] holds one count per timed-out step from the net's Adam and one from each clipped
-            # Discriminator update, plus the non-finite refusals (counted only on steps that did not time out)
-            # (the voiceprint encoder's Adam counts every refusal a second time; it runs with neither clip nor
-            # adversary)
-            timed_out = (refused - nf - nf_adv) // (1 + (n_disc if self.adv_clip_norm is not None else 0) +
-                                                    (1 if self.vnet is not None else 0))
-            self.step_count -= timed_out + nf
-            self.skipped_nonfinite += nf
-            if self.adversary is not None:  # a timed-out step refused the Discriminator's updates too
-                self.adv_step_count -= timed_out * n_disc + nf_adv
-                self.adv_skipped_nonfinite += nf_adv
+            # (optimizer, updates per step) on this status word; the voiceprint encoder's steps with the net's count
+            opts = [(self.opt, 1)] + ([(self.adv_opt, self.adv.updates)] if self.adv is not None else [])
+            timed_out = adam.timed_out_steps(refused, opts + ([(self.vp.opt, 1)] if self.vp is not None else []))
+            for opt, n in opts:  # a timed-out step refused the Discriminator's updates too
+                opt.settle(timed_out, n)
             if not (s or timed_out):
                 return
             self.rnn_ws_all.zero_()  # a timed-out launch's half-written hand-offs must not reach the next
-            if self.vnet is not None:
-                self.vp_enc.rnn_ws.zero_()
+            if self.vp is not None:
+                self.vp.enc.rnn_ws.zero_()
             where = "on this rank" if s else "on a data-parallel peer"
             raise RuntimeError(f"BiRNN hand-off timed out {where} (status {s}): {timed_out} update(s) refused")

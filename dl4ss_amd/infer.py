@@ -25,8 +25,8 @@ import math
 import torch
 
 from . import _lib, ops
-from .engine import CELLS, FlatParams, _ngate
-from .ops import A_SPLIT, W_SPLIT, hilo, pad8
+from .ops import A_SPLIT, CELLS, W_SPLIT, hilo, pad8
+from .params import FlatParams, _ngate
 
 
 class _SplitWeights:

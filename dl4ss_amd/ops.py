@@ -411,10 +411,39 @@ def adam_(p, g, m, v, step, lr=2e-4, betas=(0.9, 0.999), eps=1e-8, status=None, 
               float(gscale), _lib.ptr(loss), _lib.stream_ptr())
 
 
+# the Discriminator's launch sequences, over the caller's buffers (autograd's Functions, the adversarial step)
+def disc_forward(prec, maps, params, ys, logit, score):
+    """maps (N, T, F) -> score (N): three convs and the head.  ``params``: the eight parameters in state_dict
+    order (cnn, cnn1, cnn2, final; weight, bias); ``ys``: the three channels-last activations."""
+    w1, b1, w2, b2, w3, b3, wf, bf = (_lib.ptr(p) for p in params)
+    (N, T, F), (y1, y2, y3), st = maps.shape, ys, _lib.stream_ptr()
+    _lib.call("dl4ss_disc_conv1_fwd", prec, _lib.ptr(maps), w1, b1, N, T, F, _lib.ptr(y1), st)
+    for x, y, w, b in ((y1, y2, w2, b2), (y2, y3, w3, b3)):
+        _lib.call("dl4ss_disc_conv64_fwd", prec, _lib.ptr(x), w, b, N, x.shape[1], x.shape[2], _lib.ptr(y), st)
+    _lib.call("dl4ss_disc_head_fwd", prec, _lib.ptr(y3), wf, bf, N, y3.shape[1], y3.shape[2], _lib.ptr(logit),
+              _lib.ptr(score), st)
+
+
+def disc_backward(prec, maps, weights, ys, dys, score, dscore, target, loss, dz, grads, dx, ws, ws_bytes):
+    """The backward of disc_forward from ``dscore`` (N), or (dscore None) from the head's fused loss
+    mean_n (score_n - target)^2 -> ``loss``.  ``weights``: cnn, cnn1, cnn2, final; ``grads``: the eight parameter
+    gradients in state_dict order; ``dys``: scratch like ``ys``; ``dx`` (N, T, F) or None: the input gradient."""
+    w1, w2, w3, wf = (_lib.ptr(w) for w in weights)
+    dw1, db1, dw2, db2, dw3, db3, dwf, dbf = (_lib.ptr(g) for g in grads)
+    (N, T, F), (y1, y2, y3), (d1, d2, d3), ws, st = maps.shape, ys, dys, _lib.ptr(ws), _lib.stream_ptr()
+    _lib.call("dl4ss_disc_head_bwd", prec, _lib.ptr(y3), wf, _lib.ptr(score), _lib.ptr(dscore), float(target), N,
+              y3.shape[1], y3.shape[2], _lib.ptr(loss), _lib.ptr(dz), dwf, dbf, _lib.ptr(d3), st)
+    for x, y, dy, w, dx_, dw, db in ((y2, y3, d3, w3, d2, dw3, db3), (y1, y2, d2, w2, d1, dw2, db2)):
+        _lib.call("dl4ss_disc_conv64_bwd", prec, _lib.ptr(x), _lib.ptr(y), _lib.ptr(dy), w, N, x.shape[1], x.shape[2],
+                  _lib.ptr(dx_), dw, db, ws, ws_bytes, st)
+    _lib.call("dl4ss_disc_conv1_bwd", prec, _lib.ptr(maps), _lib.ptr(y1), _lib.ptr(d1), w1, N, T, F, _lib.ptr(dx), dw1,
+              db1, ws, ws_bytes, st)
+
+
 # ---------------------------------------------------------------------------
 # the bidirectional recurrence
 # ---------------------------------------------------------------------------
-CELLS = {"lstm": 0, "gru": 1}
+CELLS ={"lstm": 0, "gru": 1}
 # flags OR-ed into the recurrence entry points' precision argument (include/dl4ss_hip.h)
 WS_ZEROED = 0x100  # DL4SS_RNN_WS_ZEROED: the caller keeps the hand-off workspace zeroed
 DGH_PAD8 = 0x200  # DL4SS_RNN_DGH_PAD8: each direction's bf16 dGh columns start 16-B aligned

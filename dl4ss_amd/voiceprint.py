@@ -20,7 +20,8 @@ import math
 import torch
 
 from . import _lib, ops
-from .engine import FlatParams
+from .adam import GuardedAdam
+from .params import FlatParams
 
 EPS = 2.220446049250313e-16  # np.spacing(1)
 
@@ -181,6 +182,44 @@ class VoiceprintEncoder:
             self.status.zero_()
             self.rnn_ws.zero_()
             raise RuntimeError(f"BiRNN hand-off timed out (status {s})")
+
+
+class VoiceprintStep:
+    """The voiceprint queries of a training step (SepTrainer(voiceprint=, memory=)): the encoder over the step's clean
+    magnitudes ``mag_src`` (B, K, T, F), the memory, the encoder's guarded Adam and the memory refresh.  ``spk``,
+    ``q``, ``dq``, ``status``, ``loss``: the trainer's buffers (the trainer itself is not referenced: _ws_slot)."""
+
+    def __init__(self, vnet, memory, refresh, mag_src, spk, q, dq, status, loss, lr, betas, eps):
+        B, K, T, F = mag_src.shape
+        f32 = dict(device=vnet.device, dtype=torch.float32)
+        self.net, self.memory, self.refresh = vnet, memory, refresh
+        self.maps, self.spk, self.q, self.dq = mag_src.view(B * K, T, F), spk.view(-1), q, dq.view(B * K, -1)
+        self.enc = VoiceprintEncoder(vnet, B * K, T, status=status)  # its recurrences share the step's status word
+        self.u, self.dv, self.q2 = (torch.empty(B * K, vnet.E, **f32) for _ in range(3))  # q2: the refreshed rows
+        self.opt = GuardedAdam(vnet.flat, status, loss, lr, betas, eps)
+
+    def queries(self, q):
+        """q (B, K, E) = the memory rows of the step's speakers with this batch's unit voiceprints accumulated:
+        the masked encoder over the clean magnitudes the step's STFT wrote (silent frames, e.g. the zero tail of
+        a short source, are masked: rule 'nonzero'), then the memory forward.  (The STFT transforms frames in
+        pairs: a silent frame that shares its transform with a voiced one -- the first silent frame behind an odd
+        number of voiced ones -- carries that neighbour's rounding residue, ~1e-8 of it, and counts as valid.)"""
+        ops.spk_memory_fwd(self.enc.forward(self.maps), self.spk, self.memory.mem, u=self.u, q=q.view(self.u.shape))
+
+    def backward(self):
+        """dq -> the voiceprints' gradient through the memory, then the encoder's BPTT into net.grad (all written)."""
+        ops.spk_memory_bwd(self.dq, self.enc.vec, self.u, self.spk, self.memory.mem, dv=self.dv)
+        self.enc.backward(self.dv)
+
+    def optimizer_step(self, step):
+        """The encoder's guarded Adam at the mask net's count ``step`` (refused with the net's), then the memory
+        refresh, skipped on device with a refused update: "reference" re-encodes first (nnet.py:131-135)."""
+        self.opt.step(self.net.grad, step=step)
+        q = self.q
+        if self.refresh == "reference":
+            q = self.q2
+            self.queries(q)
+        ops.spk_memory_store(q.view(self.u.shape), self.spk, self.memory.mem, status=self.enc.status)
 
 
 def unit(vec):
