@@ -26,6 +26,9 @@ SIGNATURES = {
     "dl4ss_istft": [P, LL, I, I, I, I, P, P],
     "dl4ss_mix_sources": [P, P, I, I, I, P, P, P, P],
     "dl4ss_gemm": [I, I, I, I, I, P, LL, P, LL, P, LL, P, I, F, I, I, P],
+    "dl4ss_gemm_fixed": [I, I, I, I, I, P, LL, P, LL, P, LL, P, I, F, I, I, P, LL, P],
+    "dl4ss_gemm_fixed_ws_bytes": [I, I, I, I],
+    "dl4ss_gemm_fixed_kps": [I, I],
     "dl4ss_f32_to_bf16": [P, P, LL, P],
     "dl4ss_f32_to_bf16_2d": [P, LL, I, I, P, LL, P],
     "dl4ss_f32_to_bf16_hilo": [P, LL, I, I, P, LL, I, I, U, P],
@@ -123,7 +126,8 @@ RESTYPES = {"dl4ss_birnn_workspace_bytes": ctypes.c_longlong, "dl4ss_colsum_bf16
             "dl4ss_gemm_bf16_gl_grouped_ws_bytes": ctypes.c_longlong, "dl4ss_attn_nblk": ctypes.c_int,
             "dl4ss_attn_dot_nblk": ctypes.c_int, "dl4ss_attn_align_nblk": ctypes.c_int,
             "dl4ss_attn_align_part_floats": ctypes.c_longlong, "dl4ss_disc_ws_bytes": ctypes.c_longlong,
-            "dl4ss_vp_colsum_parts": ctypes.c_longlong, "dl4ss_debug_set_spin_limit": None,
+            "dl4ss_vp_colsum_parts": ctypes.c_longlong, "dl4ss_gemm_fixed_ws_bytes": ctypes.c_longlong,
+            "dl4ss_gemm_fixed_kps": ctypes.c_int, "dl4ss_debug_set_spin_limit": None,
             "dl4ss_debug_set_place_force": None, "dl4ss_debug_set_rnn_max_wg": None}
 
 _lib = None

@@ -16,7 +16,9 @@
 // contiguity (k-contiguous rows padded to an odd stride, or r-contiguous
 // k-rows), so both global reads and fragment reads are conflict-free.
 // Split-K (grid.z) accumulates with fp32 atomics into C (used for the weight
-// gradients, whose K = B*T is long and whose tile count is small).
+// gradients, whose K = B*T is long and whose tile count is small), or (dl4ss_gemm_fixed)
+// stores each k-range's tile into its own fp32 slab, which gemm_fixed_combine_kernel sums in
+// the order z = 0..S-1: the same bits on every launch.
 #include "common.h"
 #include <type_traits>
 #include <hip/hip_bf16.h>
@@ -31,6 +33,9 @@ typedef short bf16x8 __attribute__((ext_vector_type(8)));
 
 enum { EPI_NONE = 0, EPI_TANH = 1 };
 enum { PREC_F32 = 0, PREC_BF16 = 1 };
+// where gemm_kernel's accumulator tile goes: C (bias, beta, epilogue), atomically onto C, or
+// plainly into slab blockIdx.z of the split-K workspace (no bias, no beta, no epilogue)
+enum { OUT_STORE = 0, OUT_ATOMIC = 1, OUT_SLAB = 2 };
 
 __device__ __forceinline__ unsigned short f2bf(float f) {
   // round-to-nearest-even (NaN-safe enough for activations/weights)
@@ -102,7 +107,7 @@ __device__ __forceinline__ bf16x8 frag_bf16(const unsigned short* s, int r0, int
   return v;
 }
 
-template <bool A_KC, bool B_KC, int PREC, int EPI, bool ATOMIC>
+template <bool A_KC, bool B_KC, int PREC, int EPI, int OUT>
 __global__ __launch_bounds__(NT, 2) void gemm_kernel(int M, int N, int K, const float* __restrict__ A, long long lda,
                                                      const float* __restrict__ B, long long ldb,
                                                      float* __restrict__ C, long long ldc,
@@ -183,7 +188,10 @@ __global__ __launch_bounds__(NT, 2) void gemm_kernel(int M, int N, int K, const 
   }
 
   // epilogue: acc[i][j][r] -> row (r&3) + 8*(r>>2) + 4*(lane>>5), col lane&31
-  const bool add_bias = bias && blockIdx.z == 0;
+  // (OUT_SLAB: C is the workspace, ldc = N; slab z is the dense M x N matrix at C + z M N, written with
+  // the store pattern of the plain epilogue: 32 lanes on 128 contiguous bytes of a row)
+  const bool add_bias = OUT != OUT_SLAB && bias && blockIdx.z == 0;
+  if constexpr (OUT == OUT_SLAB) C += (long long)blockIdx.z * M * N;
 #pragma unroll
   for (int i = 0; i < 2; ++i)
 #pragma unroll
@@ -197,7 +205,9 @@ __global__ __launch_bounds__(NT, 2) void gemm_kernel(int M, int N, int K, const 
         if (row >= M) continue;
         float v = acc[i][j][r] + bv;
         float* cp = C + (long long)row * ldc + col;
-        if constexpr (ATOMIC) {
+        if constexpr (OUT == OUT_SLAB) {
+          *cp = v;
+        } else if constexpr (OUT == OUT_ATOMIC) {
           atomicAdd(cp, v);
         } else {
           if (beta != 0.0f) v += beta * *cp;
@@ -433,15 +443,97 @@ int launch_prec(int M, int N, int K, const float* A, long long lda, const float*
   if (splitk > 1) {
     // split-K accumulates into C (C += op(A) op(B)); no epilogue
     if (epi != EPI_NONE || beta != 1.0f) return (int)hipErrorInvalidValue;
-    hipLaunchKernelGGL((gemm_kernel<A_KC, B_KC, PREC, EPI_NONE, true>), grid, dim3(NT), 0, st, M, N, K, A, lda, B,
+    hipLaunchKernelGGL((gemm_kernel<A_KC, B_KC, PREC, EPI_NONE, OUT_ATOMIC>), grid, dim3(NT), 0, st, M, N, K, A, lda, B,
                        ldb, C, ldc, bias, beta, kps, gm);
   } else if (epi == EPI_TANH) {
-    hipLaunchKernelGGL((gemm_kernel<A_KC, B_KC, PREC, EPI_TANH, false>), grid, dim3(NT), 0, st, M, N, K, A, lda,
+    hipLaunchKernelGGL((gemm_kernel<A_KC, B_KC, PREC, EPI_TANH, OUT_STORE>), grid, dim3(NT), 0, st, M, N, K, A, lda,
                        B, ldb, C, ldc, bias, beta, kps, gm);
   } else {
-    hipLaunchKernelGGL((gemm_kernel<A_KC, B_KC, PREC, EPI_NONE, false>), grid, dim3(NT), 0, st, M, N, K, A, lda,
+    hipLaunchKernelGGL((gemm_kernel<A_KC, B_KC, PREC, EPI_NONE, OUT_STORE>), grid, dim3(NT), 0, st, M, N, K, A, lda,
                        B, ldb, C, ldc, bias, beta, kps, gm);
   }
+  DL4SS_CHECK_LAUNCH();
+  return 0;
+}
+
+// ---------------------------------------------------------------------------
+// Fixed-order split-K of the fp32 kernel: gemm_kernel<OUT_SLAB> leaves the S k-ranges' tiles in S
+// dense M x N fp32 slabs, the combine adds them in the order z = 0..S-1 (the arithmetic of
+// gemm_gl_reduce_kernel).  The k-ranges are launch_prec's, so slab z is bitwise the unsplit
+// kernel on K slice z, and the result is the same on every launch.
+// ---------------------------------------------------------------------------
+constexpr int F32_BK = 16;
+
+// the k-range of one slab: ceil(K / splitk) rounded up to the k-tile (launch_prec's rule)
+inline int fixed_kps(int K, int splitk) {
+  if (splitk < 1) splitk = 1;
+  const int kps = (K + splitk - 1) / splitk;
+  return (kps + F32_BK - 1) / F32_BK * F32_BK;
+}
+inline int fixed_slabs(int K, int splitk) {
+  const int kps = fixed_kps(K, splitk);
+  return kps > 0 ? (K + kps - 1) / kps : 1;
+}
+
+// C = sum_{z < S} part[z] (+ bias) (+ beta C): a = p_0, a += p_z in order, a += bias[c],
+// a = fmaf(beta, C, a) (explicit: no dependence on the compiler's contraction).  C is not read when
+// beta == 0; only columns < N are written.  VEC: four columns per thread with 16-B loads / stores
+// (N % 4 == 0, ldc % 4 == 0, 16-B aligned C and part), the slab loads issued eight at a time before
+// they are summed; per element the arithmetic and its order are the scalar path's.
+template <bool VEC>
+__global__ __launch_bounds__(256) void gemm_fixed_combine_kernel(int M, int N, int S, const float* __restrict__ part,
+                                                                 float* __restrict__ C, long long ldc,
+                                                                 const float* __restrict__ bias, float beta) {
+  constexpr int W = VEC ? 4 : 1;
+  const long long i = ((long long)blockIdx.x * 256 + threadIdx.x) * W;
+  const long long mn = (long long)M * N;
+  if (i >= mn) return;
+  const float* p = part + i;
+  const int r = (int)(i / N), c = (int)(i - (long long)r * N);
+  float* cp = C + (long long)r * ldc + c;
+  if constexpr (VEC) {
+    float4 a = *reinterpret_cast<const float4*>(p);
+    for (int z0 = 1; z0 < S; z0 += 8) {
+      float4 v[8];
+#pragma unroll
+      for (int u = 0; u < 8; ++u)
+        v[u] = z0 + u < S ? *reinterpret_cast<const float4*>(p + (long long)(z0 + u) * mn) : make_float4(0.f, 0.f, 0.f, 0.f);
+#pragma unroll
+      for (int u = 0; u < 8; ++u) {
+        if (z0 + u < S) { a.x += v[u].x; a.y += v[u].y; a.z += v[u].z; a.w += v[u].w; }
+      }
+    }
+    if (bias) { a.x += bias[c]; a.y += bias[c + 1]; a.z += bias[c + 2]; a.w += bias[c + 3]; }
+    if (beta != 0.0f) {
+      const float4 o = *reinterpret_cast<const float4*>(cp);
+      a.x = fmaf(beta, o.x, a.x); a.y = fmaf(beta, o.y, a.y); a.z = fmaf(beta, o.z, a.z); a.w = fmaf(beta, o.w, a.w);
+    }
+    *reinterpret_cast<float4*>(cp) = a;
+  } else {
+    float a = p[0];
+    for (int z = 1; z < S; ++z) a += p[(long long)z * mn];
+    if (bias) a += bias[c];
+    if (beta != 0.0f) a = fmaf(beta, *cp, a);
+    *cp = a;
+  }
+}
+
+template <bool A_KC, bool B_KC>
+int launch_fixed(int M, int N, int K, const float* A, long long lda, const float* B, long long ldb, float* C,
+                 long long ldc, const float* bias, float beta, int splitk, float* ws, hipStream_t st) {
+  const int gm = (M + BM - 1) / BM, gn = (N + BN - 1) / BN;
+  const int kps = fixed_kps(K, splitk), S = fixed_slabs(K, splitk);
+  hipLaunchKernelGGL((gemm_kernel<A_KC, B_KC, PREC_F32, EPI_NONE, OUT_SLAB>), dim3(gm * gn, 1, S), dim3(NT), 0, st, M,
+                     N, K, A, lda, B, ldb, ws, (long long)N, nullptr, 0.0f, kps, gm);
+  DL4SS_CHECK_LAUNCH();
+  const long long mn = (long long)M * N;
+  const bool vec = N % 4 == 0 && ldc % 4 == 0 && ((uintptr_t)C & 15) == 0 && ((uintptr_t)ws & 15) == 0;
+  if (vec)
+    hipLaunchKernelGGL(gemm_fixed_combine_kernel<true>, dim3(cdiv(mn / 4, 256)), dim3(256), 0, st, M, N, S, ws, C,
+                       ldc, bias, beta);
+  else
+    hipLaunchKernelGGL(gemm_fixed_combine_kernel<false>, dim3(cdiv(mn, 256)), dim3(256), 0, st, M, N, S, ws, C, ldc,
+                       bias, beta);
   DL4SS_CHECK_LAUNCH();
   return 0;
 }
@@ -469,4 +561,38 @@ DL4SS_API int dl4ss_gemm(int transA, int transB, int M, int N, int K, const floa
   if (a_kc && !b_kc) return launch<true, false>(precision, M, N, K, A, lda, B, ldb, C, ldc, bias, epilogue, beta, splitk, st);
   if (!a_kc && b_kc) return launch<false, true>(precision, M, N, K, A, lda, B, ldb, C, ldc, bias, epilogue, beta, splitk, st);
   return launch<false, false>(precision, M, N, K, A, lda, B, ldb, C, ldc, bias, epilogue, beta, splitk, st);
+}
+
+// The k-range of one slab of dl4ss_gemm_fixed (the last slab may be shorter); S = ceil(K / kps).
+DL4SS_API int dl4ss_gemm_fixed_kps(int K, int splitk) { return K > 0 ? fixed_kps(K, splitk) : 0; }
+
+// Bytes of split-K workspace dl4ss_gemm_fixed needs: S M N fp32, 0 when S == 1 (-1: bad arguments).
+DL4SS_API long long dl4ss_gemm_fixed_ws_bytes(int M, int N, int K, int splitk) {
+  if (M < 0 || N < 0 || K < 0) return -1;
+  const int S = fixed_slabs(K, splitk);
+  return (S <= 1 || M == 0 || N == 0) ? 0 : (long long)S * M * N * 4;
+}
+
+// dl4ss_gemm with a fixed-order split-K (fp32): the S = ceil(K / kps) k-ranges go to S fp32 slabs in ws,
+// then C = ((p_0 + p_1) + ... + p_{S-1}) (+ bias) (+ beta C) -- any beta, no atomics, the same bits on every
+// launch.  S == 1: exactly dl4ss_gemm's unsplit launch (any epilogue, any precision).  S > 1: EPI_NONE and
+// PREC_F32 only, ws of dl4ss_gemm_fixed_ws_bytes bytes.
+DL4SS_API int dl4ss_gemm_fixed(int transA, int transB, int M, int N, int K, const float* A, long long lda,
+                               const float* B, long long ldb, float* C, long long ldc, const float* bias,
+                               int epilogue, float beta, int precision, int splitk, void* ws, long long ws_bytes,
+                               void* stream) {
+  DL4SS_REQUIRE(M >= 0 && N >= 0 && K >= 0 && A && B && C);
+  if (M == 0 || N == 0) return 0;
+  const int S = fixed_slabs(K, splitk);
+  if (S <= 1)
+    return dl4ss_gemm(transA, transB, M, N, K, A, lda, B, ldb, C, ldc, bias, epilogue, beta, precision, 1, stream);
+  DL4SS_REQUIRE(epilogue == EPI_NONE && precision == PREC_F32 && S <= 65535);
+  DL4SS_REQUIRE(ws && ws_bytes >= (long long)S * M * N * 4 && ((uintptr_t)ws & 3) == 0);
+  hipStream_t st = as_stream(stream);
+  float* w = static_cast<float*>(ws);
+  const bool a_kc = !transA, b_kc = transB;
+  if (a_kc && b_kc) return launch_fixed<true, true>(M, N, K, A, lda, B, ldb, C, ldc, bias, beta, splitk, w, st);
+  if (a_kc && !b_kc) return launch_fixed<true, false>(M, N, K, A, lda, B, ldb, C, ldc, bias, beta, splitk, w, st);
+  if (!a_kc && b_kc) return launch_fixed<false, true>(M, N, K, A, lda, B, ldb, C, ldc, bias, beta, splitk, w, st);
+  return launch_fixed<false, false>(M, N, K, A, lda, B, ldb, C, ldc, bias, beta, splitk, w, st);
 }

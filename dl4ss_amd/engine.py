@@ -43,15 +43,22 @@ class SepTrainer:
     the batch's speakers are rewritten after every applied update: ``memory_refresh`` "reference" re-encodes
     with the updated weights first (nnet.py:131-135), "reuse" stores the step's own queries.  fp32, mode
     "label", single GPU, eager only; everything else is refused (plan.check_args).  None (the default): no launch is
-    added and no line of the step changes."""
+    added and no line of the step changes.
+
+    ``splitk_reduce`` "fixed" (precision "fp32" only): every backward GEMM of the step splits K through fp32 slabs
+    that are added in a fixed order (ops.gemm(reduce="fixed"), one trainer-owned workspace) -- 'align', which runs
+    them unsplit otherwise, too -- the bias gradients are fixed-order column sums (ops.vp_colsum), and with
+    ``voiceprint`` the encoder's weight gradients split the same way: losses, gradients and parameters repeat bit
+    for bit from run to run, eager or replayed.  "atomic" (the default): the step as it was."""
 
     def __init__(self, net, batch, k, n_samples, mode="label", precision="fp32", lr=2e-4, sum_weight=0.5,
                  loss_channels=None, betas=(0.9, 0.999), eps=1e-8, process_group=None, rnn_precision=None,
                  adversary=None, adv_weight=1.0, adv_lr=None, disc_adv_update=True, clip_norm=None,
-                 adv_clip_norm=None, voiceprint=None, memory=None, voiceprint_lr=None, memory_refresh="reference"):
+                 adv_clip_norm=None, voiceprint=None, memory=None, voiceprint_lr=None, memory_refresh="reference",
+                 splitk_reduce="atomic"):
         self.clip_norm, self.adv_clip_norm = check_args(  # every refusal, before any device call
             net, batch, k, n_samples, mode, precision, rnn_precision, loss_channels, process_group, adversary,
-            clip_norm, adv_clip_norm, voiceprint, memory, memory_refresh)
+            clip_norm, adv_clip_norm, voiceprint, memory, memory_refresh, splitk_reduce=splitk_reduce)
         self.vnet, self.memory, self.memory_refresh, self.adversary = voiceprint, memory, memory_refresh, adversary
         self.align = getattr(net, "attention", "dot") == "align"
         # rnn_precision, fast, split, split_x2, grouped, _ws_fill, dh_split, dh_slabs, xw, xw_kmax, xw_split0, buckets,
@@ -63,6 +70,13 @@ class SepTrainer:
         # varies from launch to launch).  The 'align' step keeps every GEMM in one piece instead, so that its
         # gradients are bitwise reproducible, eager or replayed
         self._sk = 1 if self.align else "auto"
+        # splitk_reduce "fixed" (fp32): every backward GEMM splits ("auto", 'align' too) through fp32 slabs added
+        # in a fixed order (ops.gemm(reduce="fixed")) and the bias gradients are fixed-order column sums
+        # (ops.vp_colsum): the whole step repeats bit for bit.  Both workspaces are allocated below
+        self.splitk_reduce = splitk_reduce
+        self._gk = {}
+        if splitk_reduce == "fixed":
+            self._sk = "auto"
         self.pg = process_group
         # data parallel: the gradient is all-reduced with SUM and Adam applies 1 / world
         self.world = dp.world(process_group) if process_group is not None else 1
@@ -98,6 +112,15 @@ class SepTrainer:
         self.dGh = torch.empty(BT, 2 * NGH, **f32) if net.cell == "gru" else None
         self.dH = [torch.empty(BT, 2 * H, **f32), torch.empty(BT, 2 * H, **f32)]
         self.V = torch.empty(BT, FE, **f32)  # tanh output; overwritten in place by dPre
+        if splitk_reduce == "fixed":
+            # one slab workspace for the largest request of the backward's GEMMs (dW_lin, dH, every layer's dW_ih,
+            # dW_hh and dX), allocated here so that capture() never allocates
+            shapes = [(FE, 2 * H, BT), (BT, 2 * H, FE), (NGH, H, BT), (BT, 2 * H, 2 * NGH)]
+            shapes += [(2 * NGH, F if l == 0 else 2 * H, BT) for l in range(net.L)]
+            nb = max(ops.gemm_fixed_ws_bytes(*s, "auto") for s in shapes)
+            self.fixed_ws = torch.empty(max(nb, 4) // 4, **f32)
+            self.cs_part = ops.vp_colsum_part(BT, max(FE, 2 * NGH), dev)
+            self._gk = dict(reduce="fixed", ws=self.fixed_ws)
         W = net.W
         self.q = torch.empty(B, K, W, **f32)
         self.mean = torch.empty(B, 2 * H, **f32)
@@ -147,7 +170,8 @@ class SepTrainer:
                 self.adv_grad_norm = self.adv_opt.grad_norm  # [grad_dis | grad_adv]
         if voiceprint is not None:
             self.vp = VoiceprintStep(voiceprint, memory, memory_refresh, self.mag_src, self.spk, self.q, self.dq,
-                                     self.status, self.loss, lr if voiceprint_lr is None else voiceprint_lr, betas, eps)
+                                     self.status, self.loss, lr if voiceprint_lr is None else voiceprint_lr, betas, eps,
+                                     wgrad_split="auto" if splitk_reduce == "fixed" else 1)
             self.vp_enc, self.vp_opt = self.vp.enc, self.vp.opt
         if not self.fast:
             return
@@ -640,10 +664,20 @@ class SepTrainer:
         dPre = self.V
         hL = self.out[-1].view(self.B * self.T, 2 * H)
         # grads were zeroed above: weight gradients accumulate (beta 1) with split-K
+        # (splitk_reduce "fixed": _gk selects the fixed-order reduce and the trainer's slab workspace)
         ops.gemm(dPre, hL, transA=True, out=net.view("mix.Linear.weight", g), beta=1.0, splitk=self._sk,
-                 precision=self.precision)
-        ops.colsum(dPre, net.view("mix.Linear.bias", g))
-        ops.gemm(dPre, net.view("mix.Linear.weight"), out=self.dH[0], splitk=self._sk, precision=self.precision)
+                 precision=self.precision, **self._gk)
+        self._colsum(dPre, net.view("mix.Linear.bias", g))
+        ops.gemm(dPre, net.view("mix.Linear.weight"), out=self.dH[0], splitk=self._sk, precision=self.precision,
+                 **self._gk)
+
+    def _colsum(self, A, out):
+        """A bias gradient: the column sums of A added into the zeroed gradient (ops.colsum: row blocks added
+        atomically), or (splitk_reduce "fixed") written over it in a fixed order (ops.vp_colsum): the same values."""
+        if self._gk:
+            ops.vp_colsum(A, out, self.cs_part)
+        else:
+            ops.colsum(A, out)
 
     def _query_bwd(self):
         """SPEECH_EMBEDDING / ADDJUST backward: the embedding and ADDJUST gradients (added into the
@@ -683,17 +717,19 @@ class SepTrainer:
                           status=self.status)
             xl = self.mag_mix.view(BT, -1) if l == 0 else self.out[l - 1].view(BT, 2 * H)
             ops.gemm(dG, xl, transA=True, out=net.cat_view("weight_ih", l, g), splitk=self._sk, beta=1.0,
-                     precision=self.precision)
-            ops.colsum(dG, net.cat_view("bias_ih", l, g))
+                     precision=self.precision, **self._gk)
+            self._colsum(dG, net.cat_view("bias_ih", l, g))
             whh_g = net.cat_view("weight_hh", l, g)
             hp = self.hprev[l].view(BT, 2 * H)
             for d in range(2):
                 ops.gemm(dGh[:, d * NGH:(d + 1) * NGH], hp[:, d * H:(d + 1) * H], transA=True,
-                         out=whh_g[d * NGH:(d + 1) * NGH], splitk=self._sk, beta=1.0, precision=self.precision)
-            ops.colsum(dGh, net.cat_view("bias_hh", l, g))
+                         out=whh_g[d * NGH:(d + 1) * NGH], splitk=self._sk, beta=1.0, precision=self.precision,
+                         **self._gk)
+            self._colsum(dGh, net.cat_view("bias_hh", l, g))
             if l > 0:
                 dH_next = self.dH[1] if dH is self.dH[0] else self.dH[0]
-                ops.gemm(dG, net.cat_view("weight_ih", l), out=dH_next, splitk=self._sk, precision=self.precision)
+                ops.gemm(dG, net.cat_view("weight_ih", l), out=dH_next, splitk=self._sk, precision=self.precision,
+                         **self._gk)
                 dH = dH_next
         self._status_flag()
 

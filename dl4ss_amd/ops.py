@@ -123,14 +123,48 @@ def auto_splitk(M, N, K, target_wgs=1024, min_k=512):
     return int(s)
 
 
+_fixed_ws = {}
+
+
+def _fixed_workspace(dev, nbytes):
+    """split-K slab workspace of dl4ss_gemm_fixed, one per device and stream, grown on demand
+    (never inside a graph capture: an eager call sizes it first, or the caller passes its own)"""
+    key = (dev, torch.cuda.current_stream().cuda_stream)
+    ws = _fixed_ws.get(key)
+    if ws is None or ws.numel() < nbytes:
+        if torch.cuda.is_current_stream_capturing():
+            raise RuntimeError("gemm(reduce='fixed'): split-K workspace must be sized before graph capture")
+        ws = _fixed_ws[key] = torch.empty(max(nbytes, 1 << 20), dtype=torch.uint8, device=dev)
+    return ws
+
+
+def gemm_fixed_ws_bytes(M, N, K, splitk):
+    """Bytes of split-K workspace gemm(reduce="fixed") needs for this shape and factor (an int or "auto");
+    0 when the effective split is 1."""
+    if splitk == "auto":
+        splitk = auto_splitk(M, N, K)
+    nb = int(_lib.query("dl4ss_gemm_fixed_ws_bytes", int(M), int(N), int(K), int(splitk)))
+    if nb < 0:
+        raise RuntimeError(f"gemm_fixed_ws_bytes: bad shape {(M, N, K)}")
+    return nb
+
+
 def gemm(A, B, transA=False, transB=False, bias=None, epilogue=EPI_NONE, beta=0.0, out=None, precision="fp32",
-         splitk=1):
+         splitk=1, reduce="atomic", ws=None):
     """out = op(A) @ op(B) (+ bias) (tanh) (+ beta*out).  op(A) = A.T if transA.
 
     A is stored (M, K) or (K, M) if transA; B is stored (K, N) or (N, K) if transB.
     splitk="auto": split K over workgroups (fp32 atomics) when the tile grid is small
     (needs epilogue none; a beta = 0 output is zeroed first).
+    reduce="fixed" (fp32): the split's partial tiles go to fp32 slabs that a second launch adds in a fixed
+    order (dl4ss_gemm_fixed): any beta, out neither zeroed nor read when beta = 0, the same bits on every call.
+    ws: the caller's slab workspace (a uint8 or float tensor of gemm_fixed_ws_bytes), else a per-device/stream
+    one grown on demand.
     """
+    if reduce not in ("atomic", "fixed"):
+        raise ValueError(f"gemm: reduce {reduce!r}, expected 'atomic' or 'fixed'")
+    if reduce == "atomic" and ws is not None:
+        raise ValueError("gemm: ws belongs to reduce='fixed'")
     _mat(A, "gemm(A)")
     _mat(B, "gemm(B)")
     M, K = (A.shape[1], A.shape[0]) if transA else (A.shape[0], A.shape[1])
@@ -138,7 +172,7 @@ def gemm(A, B, transA=False, transB=False, bias=None, epilogue=EPI_NONE, beta=0.
     if K != Kb:
         raise RuntimeError(f"gemm: inner dims differ ({K} vs {Kb})")
     if out is None:
-        if beta != 0.0 or splitk > 1:
+        if beta != 0.0 or (reduce == "atomic" and splitk > 1):
             raise RuntimeError("gemm: accumulation needs an output tensor")
         out = torch.empty(M, N, device=A.device, dtype=torch.float32)
     _mat(out, "gemm(out)")
@@ -146,6 +180,8 @@ def gemm(A, B, transA=False, transB=False, bias=None, epilogue=EPI_NONE, beta=0.
         raise RuntimeError(f"gemm: out shape {tuple(out.shape)} != {(M, N)}")
     if bias is not None and (bias.numel() != N or not bias.is_contiguous()):
         raise RuntimeError("gemm: bias must be contiguous with N elements")
+    if reduce == "fixed":
+        return _gemm_fixed(A, B, transA, transB, M, N, K, bias, epilogue, beta, out, precision, splitk, ws)
     if splitk == "auto":
         splitk = auto_splitk(M, N, K) if epilogue == EPI_NONE else 1
         if splitk > 1 and beta == 0.0:
@@ -156,6 +192,32 @@ def gemm(A, B, transA=False, transB=False, bias=None, epilogue=EPI_NONE, beta=0.
     _lib.call("dl4ss_gemm", int(transA), int(transB), M, N, K, _lib.ptr(A, True), A.stride(0), _lib.ptr(B, True), B.stride(0),
               _lib.ptr(out, True), out.stride(0), _lib.ptr(bias), epilogue, float(beta), PREC[precision], int(splitk),
               _lib.stream_ptr())
+    return out
+
+
+def _gemm_fixed(A, B, transA, transB, M, N, K, bias, epilogue, beta, out, precision, splitk, ws):
+    """gemm(reduce="fixed") behind gemm()'s shape checks: every refusal on the host, then dl4ss_gemm_fixed."""
+    if splitk == "auto":  # whatever beta is: the combine applies it, out is not pre-zeroed
+        splitk = auto_splitk(M, N, K) if epilogue == EPI_NONE else 1
+    splitk = int(splitk)
+    nb = gemm_fixed_ws_bytes(M, N, K, splitk)
+    if nb > 0:  # the effective split is > 1
+        if epilogue != EPI_NONE:
+            raise RuntimeError("gemm(reduce='fixed'): a split needs epilogue none")
+        if precision != "fp32":
+            raise RuntimeError(f"gemm(reduce='fixed'): a split is fp32 only, not precision {precision!r}")
+        if ws is not None:
+            if not (ws.is_cuda and ws.is_contiguous() and ws.dtype in (torch.uint8, torch.float32)):
+                raise RuntimeError("gemm(reduce='fixed'): ws must be a contiguous uint8 or float32 CUDA tensor")
+            if ws.numel() * ws.element_size() < nb:
+                raise RuntimeError(f"gemm(reduce='fixed'): workspace of {ws.numel() * ws.element_size()} bytes < {nb}")
+        else:
+            ws = _fixed_workspace(A.device, nb)
+    else:
+        ws = None
+    _lib.call("dl4ss_gemm_fixed", int(transA), int(transB), M, N, K, _lib.ptr(A, True), A.stride(0), _lib.ptr(B, True),
+              B.stride(0), _lib.ptr(out, True), out.stride(0), _lib.ptr(bias), epilogue, float(beta), PREC[precision],
+              splitk, _lib.ptr(ws), ws.numel() * ws.element_size() if ws is not None else 0, _lib.stream_ptr())
     return out
 
 

@@ -14,11 +14,16 @@ def _same_device(net, other):
 
 
 def check_args(net, batch, k, n_samples, mode, precision, rnn_precision, loss_channels, process_group, adversary,
-               clip_norm, adv_clip_norm, vnet, memory, memory_refresh):
+               clip_norm, adv_clip_norm, vnet, memory, memory_refresh, splitk_reduce="atomic"):
     """Every combination of SepTrainer's arguments it is not built for, each refused with its reason: host checks
     only, run in front of the first device call.  Returns the clip thresholds as floats (or None)."""
     if mode not in ("label", "pit", "crm"):
         raise ValueError(mode)
+    if splitk_reduce not in ("atomic", "fixed"):
+        raise ValueError(f"splitk_reduce {splitk_reduce!r}: expected 'atomic' or 'fixed'")
+    if splitk_reduce == "fixed" and precision != "fp32":
+        raise ValueError(f"splitk_reduce='fixed' is the fp32 step's fixed-order split-K (precision {precision!r}: "
+                         "the bf16 steps' split-K is already deterministic)")
     if vnet is not None or memory is not None:  # everything the voiceprint step is not built for
         if vnet is None:
             raise ValueError("memory: a SpeakerMemory needs voiceprint= (the encoder whose vectors it accumulates)")

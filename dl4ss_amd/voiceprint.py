@@ -92,14 +92,21 @@ class VoiceprintEncoder:
     next layer's compact input; then the masked mean.  ``backward`` runs the same moves in reverse around
     ``ops.birnn_bwd``; every GEMM is unsplit and the bias gradient is ``ops.vp_colsum`` (two fixed-order stages;
     ``ops.colsum`` adds its row blocks atomically), so every sum has a fixed order for any n * T and a repeated
-    call gives the same bits.  ``status``: a caller's recurrence status word (2 ints) to share; default: its own."""
+    call gives the same bits.  ``status``: a caller's recurrence status word (2 ints) to share; default: its own.
+    ``wgrad_split`` (an int or "auto", default 1: unsplit): the six weight-gradient GEMMs of ``backward`` (per
+    layer dW_ih and both directions' dW_hh, K = n * T) split over K with the fixed-order reduce
+    (``ops.gemm(reduce="fixed")``) out of one workspace allocated here: still the same bits on every call, not
+    the unsplit GEMMs' bits.  The forward, the dX GEMM and the bias gradients are the same either way."""
 
-    def __init__(self, vnet, n, T, status=None):
+    def __init__(self, vnet, n, T, status=None, wgrad_split=1):
         if not isinstance(vnet, VoiceprintNet):
             raise ValueError("VoiceprintEncoder: expected a VoiceprintNet")
         if n < 1 or not 1 <= T <= 2048:
             raise ValueError("VoiceprintEncoder: n >= 1 and 1 <= T <= 2048")
-        self.net, self.n, self.T = vnet, int(n), int(T)
+        if wgrad_split != "auto" and (isinstance(wgrad_split, bool) or not isinstance(wgrad_split, int)
+                                      or wgrad_split < 1):
+            raise ValueError(f"VoiceprintEncoder: wgrad_split {wgrad_split!r}, expected an int >= 1 or 'auto'")
+        self.net, self.n, self.T, self.wgrad_split = vnet, int(n), int(T), wgrad_split
         H, L, F, dev = vnet.H, vnet.L, vnet.F, vnet.device
         f32 = dict(device=dev, dtype=torch.float32)
         i32 = dict(device=dev, dtype=torch.int32)
@@ -123,6 +130,13 @@ class VoiceprintEncoder:
         self.ws_bytes = ws
         self.rnn_ws = torch.zeros((ws + 7) // 8, device=dev, dtype=torch.int64)
         self.status = torch.zeros(2, **i32) if status is None else status
+        # the weight gradients' shapes (M, N, K): dW_hh per direction, dW_ih of layer 0 and of the layers above
+        shapes = [(4 * H, H, n * T), (8 * H, F, n * T)] + ([(8 * H, 2 * H, n * T)] if L > 1 else [])
+        self.wgrad_ws = None
+        if wgrad_split != 1:
+            nb = max(ops.gemm_fixed_ws_bytes(*s, wgrad_split) for s in shapes)
+            self.wgrad_ws = torch.empty(max(nb, 4) // 4, **f32)
+        self._wg = {} if wgrad_split == 1 else dict(splitk=wgrad_split, reduce="fixed", ws=self.wgrad_ws)
 
     def forward(self, feats, rule="nonzero", thr=None, lengths=None):
         """feats (n, T, F) -> vec (n, E) (a buffer the next call reuses).  ``lengths`` (n) int32: a plain prefix
@@ -163,11 +177,11 @@ class VoiceprintEncoder:
             hp = self.hprev[l].view(nT, 2 * H)
             for d in range(2):
                 ops.gemm(G2[:, d * NGH:(d + 1) * NGH], hp[:, d * H:(d + 1) * H], transA=True,
-                         out=whh_g[d * NGH:(d + 1) * NGH])
+                         out=whh_g[d * NGH:(d + 1) * NGH], **self._wg)
             # the reverse columns back to the compact frame, where the layer's input lives
             ops.vp_shift(self.G, self.Gc, self.len, NGH, 2 * NGH, -1, other=2)
             xl = self.xc.view(nT, -1) if l == 0 else self.xin[l].view(nT, 2 * H)
-            ops.gemm(Gc2, xl, transA=True, out=net.cat_view("weight_ih", l, g))
+            ops.gemm(Gc2, xl, transA=True, out=net.cat_view("weight_ih", l, g), **self._wg)
             if l > 0:
                 ops.gemm(Gc2, net.cat_view("weight_ih", l), out=self.dX.view(nT, 2 * H))
                 ops.vp_shift(self.dX, self.dH, self.len, H, 2 * H, +1, other=2)
@@ -189,12 +203,13 @@ class VoiceprintStep:
     magnitudes ``mag_src`` (B, K, T, F), the memory, the encoder's guarded Adam and the memory refresh.  ``spk``,
     ``q``, ``dq``, ``status``, ``loss``: the trainer's buffers (the trainer itself is not referenced: _ws_slot)."""
 
-    def __init__(self, vnet, memory, refresh, mag_src, spk, q, dq, status, loss, lr, betas, eps):
+    def __init__(self, vnet, memory, refresh, mag_src, spk, q, dq, status, loss, lr, betas, eps, wgrad_split=1):
         B, K, T, F = mag_src.shape
         f32 = dict(device=vnet.device, dtype=torch.float32)
         self.net, self.memory, self.refresh = vnet, memory, refresh
         self.maps, self.spk, self.q, self.dq = mag_src.view(B * K, T, F), spk.view(-1), q, dq.view(B * K, -1)
-        self.enc = VoiceprintEncoder(vnet, B * K, T, status=status)  # its recurrences share the step's status word
+        # its recurrences share the step's status word
+        self.enc = VoiceprintEncoder(vnet, B * K, T, status=status, wgrad_split=wgrad_split)
         self.u, self.dv, self.q2 = (torch.empty(B * K, vnet.E, **f32) for _ in range(3))  # q2: the refreshed rows
         self.opt = GuardedAdam(vnet.flat, status, loss, lr, betas, eps)
 

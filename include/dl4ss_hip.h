@@ -92,6 +92,20 @@ enum { DL4SS_PREC_F32 = 0, DL4SS_PREC_BF16 = 1 };
 int dl4ss_gemm(int transA, int transB, int M, int N, int K, const float* A, long long lda, const float* B,
                long long ldb, float* C, long long ldc, const float* bias, int epilogue, float beta, int precision,
                int splitk, void* stream);
+/* dl4ss_gemm with a fixed-order split-K (fp32 parity mode): no atomics, the same bits on every launch.
+ * The k-ranges are dl4ss_gemm's: kps = dl4ss_gemm_fixed_kps(K, splitk) = ceil(ceil(K / splitk) / 16) * 16,
+ * S = ceil(K / kps).  Workgroup (tile, z) stores its tile into slab z of ws ([S][M][N] fp32, dense), which is
+ * bitwise the unsplit kernel on k-range z; a combine launch then forms
+ *   C = ((p_0 + p_1) + ... + p_{S-1}) (+ bias[N]) (+ beta C)
+ * in that order (beta applied as one fmaf; C is not read when beta == 0; only columns < N are written).
+ * S == 1: exactly dl4ss_gemm's unsplit launch (any epilogue or precision; ws unused).  S > 1: DL4SS_EPI_NONE
+ * and DL4SS_PREC_F32 only, any beta, optional bias; ws must hold dl4ss_gemm_fixed_ws_bytes(M, N, K, splitk)
+ * bytes (0 when S == 1), hipErrorInvalidValue otherwise. */
+int dl4ss_gemm_fixed_kps(int K, int splitk);
+long long dl4ss_gemm_fixed_ws_bytes(int M, int N, int K, int splitk);
+int dl4ss_gemm_fixed(int transA, int transB, int M, int N, int K, const float* A, long long lda, const float* B,
+                     long long ldb, float* C, long long ldc, const float* bias, int epilogue, float beta,
+                     int precision, int splitk, void* ws, long long ws_bytes, void* stream);
 
 /* y[i] = bf16(x[i]) (round to nearest even), n elements; x 16-B aligned, y 8-B aligned. */
 int dl4ss_f32_to_bf16(const float* x, void* y, long long n, void* stream);
