@@ -1,17 +1,29 @@
-"""ctypes binding of ``libdl4ss_hip.so`` (the C ABI in ``include/dl4ss_hip.h``).
+"""ctypes binding of ``libdl4ss_hip.so``, derived from the C ABI's one declaration, ``include/dl4ss_hip.h``.
 
-The product path has no CPU fallback: if the library is missing or a call
-returns a non-zero ``hipError_t`` this raises ``RuntimeError`` with the HIP error
-string.  Tensors are passed as raw device pointers; every call is enqueued on
-torch's current HIP stream.
+The header is parsed once at import: every prototype gives the entry point's ``argtypes`` (``SIGNATURES``), its
+``restype`` (``RESTYPES``) and its parameter names (``PARAMS``); every enum constant and ``#define DL4SS_* <integer>``
+lands in ``CONSTANTS``.  The same header is compiled against every definition (``csrc/common.h`` includes it), so
+the binding, the prototypes and the definitions cannot drift apart.  A declaration the parser cannot fully
+classify raises at import, with the offending text: it never guesses.
+
+``call`` and ``query`` take positional arguments, then keywords by the header's parameter names (``pass_`` and
+``lambda_`` for the two that are Python keywords); ``bind`` refuses a missing, unknown or repeated parameter and
+any argument count but the prototype's with ``TypeError``, before the library is touched.
+
+The product path has no CPU fallback: if the library is missing or a call returns a non-zero ``hipError_t`` this
+raises ``RuntimeError`` with the HIP error string.  Tensors are passed as raw device pointers; every call is
+enqueued on torch's current HIP stream.
 """
 import ctypes
+import keyword
 import os
+import re
 
 import torch
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("DL4SS_LIB", os.path.join(_HERE, "libdl4ss_hip.so"))
+HEADER = os.path.join(os.path.dirname(_HERE), "include", "dl4ss_hip.h")
 
 P = ctypes.c_void_p
 I = ctypes.c_int
@@ -19,116 +31,57 @@ LL = ctypes.c_longlong
 F = ctypes.c_float
 U = ctypes.c_uint
 
-# name -> argtypes (all return int hipError_t)
-SIGNATURES = {
-    "dl4ss_stft_fwd": [P, LL, I, I, I, I, P, P, P],
-    "dl4ss_stft_fwd_ex": [P, LL, I, I, I, I, P, P, P, LL, LL, P],
-    "dl4ss_istft": [P, LL, I, I, I, I, P, P],
-    "dl4ss_mix_sources": [P, P, I, I, I, P, P, P, P],
-    "dl4ss_gemm": [I, I, I, I, I, P, LL, P, LL, P, LL, P, I, F, I, I, P],
-    "dl4ss_gemm_fixed": [I, I, I, I, I, P, LL, P, LL, P, LL, P, I, F, I, I, P, LL, P],
-    "dl4ss_gemm_fixed_ws_bytes": [I, I, I, I],
-    "dl4ss_gemm_fixed_kps": [I, I],
-    "dl4ss_f32_to_bf16": [P, P, LL, P],
-    "dl4ss_f32_to_bf16_2d": [P, LL, I, I, P, LL, P],
-    "dl4ss_f32_to_bf16_hilo": [P, LL, I, I, P, LL, I, I, U, P],
-    "dl4ss_birnn_bias_reduce": [I, I, I, I, P, P, P, P],
-    "dl4ss_birnn_bias_reduce_ex": [I, I, I, I, P, P, P, F, P],
-    "dl4ss_colsum_bf16": [P, LL, I, I, P, P],
-    "dl4ss_colsum_bf16_part_bytes": [I, I],
-    "dl4ss_colsum_bf16_det": [P, LL, I, I, P, P, LL, P],
-    "dl4ss_colsum_bf16_det_ex": [P, LL, I, I, P, P, LL, F, P],
-    "dl4ss_gemm_bf16_gl_ws_bytes": [I, I, I, I, I],
-    "dl4ss_gemm_gl_set_config": [I],
-    "dl4ss_gemm_bf16_gl": [I, I, I, I, I, P, LL, P, LL, P, LL, P, I, F, I, I, LL, LL, LL, P, LL, P],
-    "dl4ss_gemm_bf16_gl_grouped_ws_bytes": [I, P, P, P, P],
-    "dl4ss_gemm_bf16_gl_grouped": [I, I, I, P, P, P, P, P, P, P, P, P, P, P, P, LL, P],
-    "dl4ss_gemm_bf16_gl_grouped_ex": [I, I, I, P, P, P, P, P, P, P, P, P, P, P, P, LL, I, I, I, P, P],
-    "dl4ss_birnn_fwd_ex": [I, I, I, I, I, P, P, P, P, P, P, P, P, P, P, LL, P, P],
-    "dl4ss_birnn_fwd_xw": [I, I, I, I, P, I, LL, P, LL, P, P, P, P, P, P, P, P, P, P, LL, P, P, I],
-    "dl4ss_birnn_fwd_mean": [I, I, I, I, I, P, P, P, P, P, P, P, P, P, P, P, LL, P, P],
-    "dl4ss_birnn_fwd_xw_ex": [I, I, I, I, P, I, LL, P, LL, P, P, P, P, P, P, P, P, P, P, P, LL, P, P, I],
-    "dl4ss_birnn_fwd_xw_supported": [I, I, I, I, I],
-    "dl4ss_birnn_bwd_ex": [I, I, I, I, I, P, P, P, P, P, P, P, P, P, P, P, P, P, LL, P, P],
-    "dl4ss_mask_attn_loss_ex": [I, I, I, I, I, I, I, P, P, P, LL, P, LL, LL, P, F, F, P, P, LL, P, P, P, P, P],
-    "dl4ss_birnn_workspace_bytes": [I, I, I],
-    "dl4ss_birnn_fwd": [I, I, I, I, I, P, P, P, P, P, P, P, P, LL, P, P],
-    "dl4ss_birnn_bwd": [I, I, I, I, I, P, P, P, P, P, P, P, P, P, LL, P, P],
-    "dl4ss_attn_nblk": [I, I],
-    "dl4ss_mask_attn_loss": [I, I, I, I, I, I, I, P, P, P, LL, P, LL, LL, P, F, F, P, P, P, P, P, P],
-    "dl4ss_pit_select": [P, I, I, I, P, P],
-    "dl4ss_loss_finalize": [P, I, I, I, P, F, F, P, P, I, P, P],
-    "dl4ss_query_fwd": [P, I, I, I, P, P, P, I, I, P, P, P],
-    "dl4ss_query_bwd": [P, I, I, I, P, P, P, P, I, I, P, P, P, P],
-    "dl4ss_query_bwd_ex": [P, I, I, I, P, P, P, P, I, I, P, P, P, I, F, P],
-    "dl4ss_colsum": [P, LL, I, I, P, P],
-    "dl4ss_adam": [P, P, P, P, LL, F, F, F, F, I, P],
-    "dl4ss_istft_apply": [P, P, LL, I, I, I, I, P, P],
-    "dl4ss_tanh_bwd": [P, P, P, LL, P],
-    "dl4ss_attn_dot_nblk": [I],
-    "dl4ss_attn_dot_fwd": [P, P, I, I, I, I, I, P, P],
-    "dl4ss_attn_dot_bwd": [P, P, I, P, P, I, I, I, I, P, P, P, P],
-    "dl4ss_top_k_mask": [P, I, I, F, I, P, P, P, P],
-    "dl4ss_attn_dot_fwd_ex": [P, P, I, I, I, I, I, P, LL, P],
-    "dl4ss_classifier_select": [P, I, I, F, I, P, I, P, P, P, P],
-    "dl4ss_mask_split": [P, P, LL, P, P, P],
-    "dl4ss_time_mean": [P, I, I, I, P, P],
-    "dl4ss_bss_corr": [P, I, I, I, I, P, P],
-    "dl4ss_mix_sources_ex": [P, P, P, I, I, I, P, P, P, P],
-    "dl4ss_mix_sources_rot": [P, P, P, P, I, I, I, P, P, P, P],
-    "dl4ss_f32_to_bf16_2d_multi": [I, P, P, P, P, P, P, P],
-    "dl4ss_mask_attn_loss_bf16v": [I, I, I, I, I, I, I, P, P, P, LL, P, LL, LL, P, F, F, P, P, LL, P, P, P, P, P],
-    "dl4ss_bss_gram": [P, I, I, I, I, P, P, P, P],
-    "dl4ss_adam_guarded": [P, P, P, P, LL, F, F, F, F, I, P, P, P],
-    "dl4ss_adam_guarded_dp": [P, P, P, P, LL, F, F, F, F, I, P, P, P, P],
-    "dl4ss_adam_guarded_dp_scaled": [P, P, P, P, LL, F, F, F, F, I, P, P, F, P, P],
-    "dl4ss_adam_guarded_dp_scaled_bf16": [P, P, P, P, LL, F, F, F, F, I, P, P, F, P, I, P, P, P, P, P, P],
-    "dl4ss_grad_sumsq_parts": [LL],
-    "dl4ss_grad_sumsq": [P, LL, P, P],
-    "dl4ss_adam_clipped": [P, P, P, P, LL, F, F, F, F, I, P, P, F, P, I, P, P, P, P, P, P, I, F, P, P, P],
-    "dl4ss_status_flag": [P, P, P],
-    "dl4ss_birnn_plan_info": [I, I, I, I, I, P],
-    "dl4ss_debug_set_spin_limit": [ctypes.c_uint],
-    "dl4ss_debug_set_place_force": [ctypes.c_int],
-    "dl4ss_debug_set_rnn_max_wg": [ctypes.c_int],
-    "dl4ss_attn_align_nblk": [I],
-    "dl4ss_attn_align_part_floats": [I, I, I],
-    "dl4ss_attn_align_fwd": [P, P, I, P, P, P, I, I, I, P, LL, P],
-    "dl4ss_attn_align_bwd": [P, P, I, P, P, P, P, I, I, I, P, P, LL, P, P, P, P, P],
-    "dl4ss_mask_attn_align_loss": [I, I, I, I, I, I, P, P, P, P, P, P, LL, P, LL, LL, P, F, F, P, P, P, LL, P, P, P],
-    "dl4ss_attn_align_finalize": [P, LL, I, I, I, I, P, P, P, P, P, P, P],
-    "dl4ss_cls_head_fwd": [P, P, P, I, I, I, P, P, P],
-    "dl4ss_cls_head_loss_bwd": [P, P, P, P, I, I, I, I, P, P, P, P, P, P],
-    "dl4ss_disc_dims": [I, I, P],
-    "dl4ss_disc_ws_bytes": [I, I, I],
-    "dl4ss_disc_conv1_fwd": [I, P, P, P, I, I, I, P, P],
-    "dl4ss_disc_conv64_fwd": [I, P, P, P, I, I, I, P, P],
-    "dl4ss_disc_head_fwd": [I, P, P, P, I, I, I, P, P, P],
-    "dl4ss_disc_head_bwd": [I, P, P, P, P, F, I, I, I, P, P, P, P, P, P],
-    "dl4ss_disc_conv64_bwd": [I, P, P, P, P, I, I, I, P, P, P, P, LL, P],
-    "dl4ss_disc_conv1_bwd": [I, P, P, P, P, I, I, I, P, P, P, P, LL, P],
-    "dl4ss_mask_attn_loss_adv": [I, I, I, I, I, P, P, P, LL, P, LL, LL, P, F, F, P, P, P, LL, P, P, P, P, P],
-    "dl4ss_mask_attn_loss_adv_bf16v": [I, I, I, I, I, P, P, P, LL, P, LL, LL, P, F, F, P, P, P, LL, P, P, P, P, P],
-    "dl4ss_disc_adv_heads": [P, I, F, P, P, P, P],
-    "dl4ss_vp_compact": [P, I, I, I, I, F, P, P, P, P, P],
-    "dl4ss_vp_shift": [P, P, I, I, I, I, I, P, I, I, P],
-    "dl4ss_vp_mean_fwd": [P, I, I, I, P, P, P],
-    "dl4ss_vp_mean_bwd": [P, I, I, I, P, P, P],
-    "dl4ss_vp_colsum_parts": [LL],
-    "dl4ss_vp_colsum": [P, LL, I, P, P, P],
-    "dl4ss_spk_memory_fwd": [P, P, P, I, I, I, P, P, P],
-    "dl4ss_spk_memory_bwd": [P, P, P, P, P, I, I, I, P, P],
-    "dl4ss_spk_memory_store": [P, P, I, I, I, P, P, P],
-}
-# entry points that return a value rather than a hipError_t
-RESTYPES = {"dl4ss_birnn_workspace_bytes": ctypes.c_longlong, "dl4ss_colsum_bf16_part_bytes": ctypes.c_longlong,
-            "dl4ss_gemm_bf16_gl_ws_bytes": ctypes.c_longlong, "dl4ss_grad_sumsq_parts": ctypes.c_longlong,
-            "dl4ss_gemm_bf16_gl_grouped_ws_bytes": ctypes.c_longlong, "dl4ss_attn_nblk": ctypes.c_int,
-            "dl4ss_attn_dot_nblk": ctypes.c_int, "dl4ss_attn_align_nblk": ctypes.c_int,
-            "dl4ss_attn_align_part_floats": ctypes.c_longlong, "dl4ss_disc_ws_bytes": ctypes.c_longlong,
-            "dl4ss_vp_colsum_parts": ctypes.c_longlong, "dl4ss_gemm_fixed_ws_bytes": ctypes.c_longlong,
-            "dl4ss_gemm_fixed_kps": ctypes.c_int, "dl4ss_debug_set_spin_limit": None,
-            "dl4ss_debug_set_place_force": None, "dl4ss_debug_set_rnn_max_wg": None}
+_VALUE = {"int": I, "long long": LL, "float": F, "unsigned": U}  # by-value parameter types
+_POINTEE = set(_VALUE) | {"void", "double"}  # what a pointer or array parameter may point at
+_RETURN = {"int": I, "long long": LL, "void": None}
+_PROTO = re.compile(r"(int|long long|void)\s+(dl4ss_\w+)\s*\(([^()]*)\)\s*;")
+_INT = r"(0[xX][0-9a-fA-F]+|\d+)"
+
+
+def parse_header(text):
+    """(signatures, restypes, params, constants) of the header ``text``: name -> argtypes list, name -> restype,
+    name -> parameter names, and the integer enum constants and object-like ``DL4SS_*`` macros."""
+    text = re.sub(r"/\*.*?\*/|//[^\n]*", " ", text, flags=re.S)
+    sigs, res, params, consts = {}, {}, {}, {}
+    for m in re.finditer(r"^(?!\s*#)[^\n]*\bdl4ss_\w+\s*\(", text, flags=re.M):  # every line that opens a prototype
+        line = m.group(0).strip()
+        proto = _PROTO.match(text, m.start())
+        if not proto:
+            raise ValueError(f"dl4ss_hip.h: cannot parse the declaration at {line!r}")
+        ret, name, plist = proto.groups()
+        argtypes, names = [], []
+        for p in plist.split(","):
+            words = [w for w in re.findall(r"[A-Za-z_]\w*", re.sub(r"\[\d*\]", "", p)) if w != "const"]
+            base, pname = " ".join(words[:-1]), words[-1] if words else ""
+            pointer = "*" in p or "[" in p
+            if base not in (_POINTEE if pointer else _VALUE) or pname in names:
+                raise ValueError(f"dl4ss_hip.h: cannot classify parameter {p.strip()!r} of {line!r} "
+                                 "(unknown type, no name or a repeated name)")
+            argtypes.append(P if pointer else _VALUE[base])
+            names.append(pname)
+        sigs[name], res[name], params[name] = argtypes, _RETURN[ret], tuple(names)
+    for m in re.finditer(r"\benum\b[^;]*;", text):  # anonymous `enum { ... };` only: any other form is refused
+        enum = re.fullmatch(r"enum\s*\{([^{}]*)\}\s*;", m.group(0))
+        if not enum:
+            raise ValueError(f"dl4ss_hip.h: cannot parse the enum at {m.group(0)[:60]!r}")
+        for item in filter(None, (x.strip() for x in enum.group(1).split(","))):
+            m = re.fullmatch(r"(\w+)\s*=\s*" + _INT, item)
+            if not m:
+                raise ValueError(f"dl4ss_hip.h: enum constant {item!r} has no integer value")
+            consts[m.group(1)] = int(m.group(2), 0)
+    for m in re.finditer(r"^#define[ \t]+(DL4SS_\w+)[ \t]+([^\n]*)$", text, flags=re.M):  # (not function-like)
+        if not re.fullmatch(_INT, m.group(2).strip()):
+            raise ValueError(f"dl4ss_hip.h: macro {m.group(0)!r} is not an integer")
+        consts[m.group(1)] = int(m.group(2).strip(), 0)
+    return sigs, res, params, consts
+
+
+with open(HEADER) as _f:
+    SIGNATURES, RESTYPES, PARAMS, CONSTANTS = parse_header(_f.read())
+# keyword -> slot of every entry point (a header name that is a Python keyword takes a trailing underscore)
+_SLOTS = {name: {p + "_" if keyword.iskeyword(p) else p: i for i, p in enumerate(ps)} for name, ps in PARAMS.items()}
+# knobs the library itself used to read from the environment, retired with plan.RETIRED_KNOBS
+RETIRED_ENV = ("DL4SS_ATTN_TILES", "DL4SS_RNN_MAX_WG", "DL4SS_RNN_MIN_BC")
 
 _lib = None
 
@@ -137,6 +90,9 @@ def _load():
     global _lib
     if _lib is not None:
         return _lib
+    for name in RETIRED_ENV:
+        if name in os.environ:
+            raise ValueError(f"{name} is retired, its default is the only path (DESIGN.md section 11): unset it")
     if not os.path.exists(LIB_PATH):
         raise RuntimeError(
             f"dl4ss HIP library not found at {LIB_PATH}; run `python -m dl4ss_amd.build` "
@@ -145,7 +101,7 @@ def _load():
     for name, argtypes in SIGNATURES.items():
         fn = getattr(lib, name)
         fn.argtypes = argtypes
-        fn.restype = RESTYPES.get(name, ctypes.c_int)
+        fn.restype = RESTYPES[name]
     hip = ctypes.CDLL("libamdhip64.so")
     hip.hipGetErrorString.restype = ctypes.c_char_p
     hip.hipGetErrorString.argtypes = [ctypes.c_int]
@@ -180,12 +136,39 @@ def ptr(t, strided=False):
     return ctypes.c_void_p(t.data_ptr())
 
 
-def query(name, *args):
+def bind(name, args, kw):
+    """The positional tuple of one call of ``name``: ``args`` first, then ``kw`` by the header's parameter names.
+    ``TypeError`` unless every parameter of the prototype is given exactly once."""
+    slots = _SLOTS.get(name)
+    if slots is None:
+        raise TypeError(f"{name} is not declared in include/dl4ss_hip.h")
+    n, given = len(slots), len(args) + len(kw)
+    if len(args) > n:
+        raise TypeError(f"{name} takes {n} arguments (the last is {PARAMS[name][-1]!r}), {given} given")
+    if not kw and given == n:
+        return tuple(args)
+    out = list(args) + [None] * (n - len(args))
+    for k, v in kw.items():
+        i = slots.get(k)
+        if i is None:
+            raise TypeError(f"{name} has no parameter {k!r}")
+        if i < len(args):
+            raise TypeError(f"{name}: parameter {k!r} given by position and by keyword")
+        out[i] = v
+    if given != n:  # the keywords are distinct and behind args, so fewer than n leaves a slot unfilled
+        missing = [k for k, i in slots.items() if i >= len(args) and k not in kw]
+        raise TypeError(f"{name}: missing parameter {missing[0]!r} ({given} of {n} given)")
+    return tuple(out)
+
+
+def query(name, *args, **kw):
     """Call an entry point that returns a value (sizes), not an error code."""
+    args = bind(name, args, kw)
     return getattr(_load(), name)(*args)
 
 
-def call(name, *args):
+def call(name, *args, **kw):
+    args = bind(name, args, kw)
     lb = _load()
     rc = getattr(lb, name)(*args)
     if rc != 0:

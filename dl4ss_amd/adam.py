@@ -52,9 +52,10 @@ class GuardedAdam:
             self.step_count += 1
             step = self.step_count
         if not self.counted:
-            _lib.call("dl4ss_adam_guarded", _lib.ptr(self.flat), _lib.ptr(grad), _lib.ptr(self.m), _lib.ptr(self.v),
-                      self.flat.numel(), float(self.lr), float(self.betas[0]), float(self.betas[1]), float(self.eps),
-                      step, _lib.ptr(self.status), _lib.ptr(self.loss), _lib.stream_ptr())
+            _lib.call("dl4ss_adam_guarded", p=_lib.ptr(self.flat), g=_lib.ptr(grad), m=_lib.ptr(self.m),
+                      v=_lib.ptr(self.v), n=self.flat.numel(), lr=float(self.lr), beta1=float(self.betas[0]),
+                      beta2=float(self.betas[1]), eps=float(self.eps), step=step, status=_lib.ptr(self.status),
+                      loss=_lib.ptr(self.loss), stream=_lib.stream_ptr())
             return
         clip = None
         if self.clip_norm is not None:

@@ -199,9 +199,9 @@ def attention_dot_bwd_impl(dmask, V, q, masks, crm, need_dV=True):
     dqh = torch.empty(Bq, E, device=V.device)
     for h, m in enumerate(masks):
         dm = _c(dmask[..., h].float()) if crm else _c(dmask.float())
-        _lib.call("dl4ss_attn_dot_bwd", _lib.ptr(V), ctypes.c_void_p(q.data_ptr() + 4 * h * E), q.shape[1],
-                  _lib.ptr(m), _lib.ptr(dm), Bq, R, E, int(crm), _lib.ptr(dV) if dV is not None else None,
-                  _lib.ptr(part), _lib.ptr(dqh), st)
+        _lib.call("dl4ss_attn_dot_bwd", V=_lib.ptr(V), q=ctypes.c_void_p(q.data_ptr() + 4 * h * E), q_stride=q.shape[1],
+                  mask=_lib.ptr(m), dmask=_lib.ptr(dm), Bq=Bq, R=R, E=E, act=int(crm),
+                  dV=_lib.ptr(dV) if dV is not None else None, part_dq=_lib.ptr(part), dq=_lib.ptr(dqh), stream=st)
         dq[:, h * E:(h + 1) * E] = dqh
     return dV, dq
 
@@ -231,8 +231,9 @@ def attention_align_fwd_impl(V, q, W1, W2, w3):
     V, q, W1, W2, w3 = (_c(t.float()) for t in (V, q, W1, W2, w3))
     Bq, R, E = V.shape
     m = torch.empty(Bq, R, device=V.device)
-    _lib.call("dl4ss_attn_align_fwd", _lib.ptr(V), _lib.ptr(q), q.shape[1], _lib.ptr(W1), _lib.ptr(W2), _lib.ptr(w3),
-              Bq, R, E, _lib.ptr(m), R, _lib.stream_ptr())
+    _lib.call("dl4ss_attn_align_fwd", V=_lib.ptr(V), q=_lib.ptr(q), q_stride=q.shape[1], W1=_lib.ptr(W1),
+              W2=_lib.ptr(W2), w3=_lib.ptr(w3), Bq=Bq, R=R, E=E, mask=_lib.ptr(m), mask_stride=R,
+              stream=_lib.stream_ptr())
     return m
 
 
@@ -248,9 +249,10 @@ def attention_align_bwd_impl(dmask, V, q, W1, W2, w3, need_dV=True):
     dV = torch.zeros_like(V) if need_dV else None
     n = _lib.query("dl4ss_attn_align_part_floats", Bq, 1, _lib.query("dl4ss_attn_align_nblk", R))
     part = torch.empty(n, device=dev)
-    _lib.call("dl4ss_attn_align_bwd", _lib.ptr(V), _lib.ptr(q), q.shape[1], _lib.ptr(W1), _lib.ptr(W2), _lib.ptr(w3),
-              _lib.ptr(dmask), Bq, R, E, _lib.ptr(dV), _lib.ptr(part), n, _lib.ptr(dq), _lib.ptr(dW1), _lib.ptr(dW2),
-              _lib.ptr(dw3), _lib.stream_ptr())
+    _lib.call("dl4ss_attn_align_bwd", V=_lib.ptr(V), q=_lib.ptr(q), q_stride=q.shape[1], W1=_lib.ptr(W1),
+              W2=_lib.ptr(W2), w3=_lib.ptr(w3), dmask=_lib.ptr(dmask), Bq=Bq, R=R, E=E, dV=_lib.ptr(dV),
+              part=_lib.ptr(part), part_floats=n, dq=_lib.ptr(dq), dW1=_lib.ptr(dW1), dW2=_lib.ptr(dW2),
+              dw3=_lib.ptr(dw3), stream=_lib.stream_ptr())
     return dV, dq, dW1, dW2, dw3
 
 
@@ -285,8 +287,8 @@ class EmbeddingGatherFn(torch.autograd.Function):
         W = emb.shape[1]
         q = torch.empty(B, K, W, device=emb.device)
         # query kernel without ADJUST: a pure gather (h / mean unused)
-        _lib.call("dl4ss_query_fwd", _lib.ptr(emb), B, 1, 1, _lib.ptr(idx), _lib.ptr(emb), None, K, W, _lib.ptr(q),
-                  None, _lib.stream_ptr())
+        _lib.call("dl4ss_query_fwd", h=_lib.ptr(emb), B=B, T=1, D=1, idx=_lib.ptr(idx), emb=_lib.ptr(emb), w_adj=None,
+                  K=K, W=W, q=_lib.ptr(q), mean_out=None, stream=_lib.stream_ptr())
         ctx.save_for_backward(idx)
         ctx.shape = emb.shape
         return q
@@ -298,8 +300,8 @@ class EmbeddingGatherFn(torch.autograd.Function):
         n, W = ctx.shape
         demb = torch.zeros(n, W, device=dq.device)
         dq = _c(dq.float())
-        _lib.call("dl4ss_query_bwd", _lib.ptr(dq), B, 1, 1, _lib.ptr(idx), None, None, None, K, W, _lib.ptr(demb),
-                  None, None, _lib.stream_ptr())
+        _lib.call("dl4ss_query_bwd", dq=_lib.ptr(dq), B=B, T=1, D=1, idx=_lib.ptr(idx), emb=None, w_adj=None, mean=None,
+                  K=K, W=W, d_emb=_lib.ptr(demb), d_wadj=None, dh_bcast=None, stream=_lib.stream_ptr())
         return demb, None
 
 

@@ -3,8 +3,10 @@
 Every ``dl4ss_amd/csrc/*.hip`` is compiled to an object with
 ``hipcc --offload-arch=gfx950 -O3 -fPIC`` (in parallel) and linked into one
 shared library next to this file.  The library exports the C ABI declared in
-``include/dl4ss_hip.h``.  Objects are rebuilt only when a source or header is
-newer than the object.
+``include/dl4ss_hip.h``: every source includes that header (through
+``csrc/common.h``), so a definition that disagrees with its prototype fails to
+compile.  Objects are rebuilt only when a source or header -- the public one
+included -- is newer than the object.
 """
 import concurrent.futures as cf
 import os
@@ -15,6 +17,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 OBJ = os.path.join(HERE, "csrc", "_obj")
 LIB = os.path.join(HERE, "libdl4ss_hip.so")
+HEADER = os.path.join(os.path.dirname(HERE), "include", "dl4ss_hip.h")  # (common.h includes it by relative path)
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 ARCH = "gfx950"
 FLAGS = ["-O3", "-fPIC", "-std=c++17", f"--offload-arch={ARCH}", "-munsafe-fp-atomics",
@@ -45,6 +48,7 @@ def build(verbose=False, jobs=None):
     os.makedirs(OBJ, exist_ok=True)
     srcs = sorted(f for f in os.listdir(CSRC) if f.endswith(".hip"))
     headers = [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".h")]
+    headers.append(HEADER)
     objs, todo = [], []
     for f in srcs:
         src = os.path.join(CSRC, f)

@@ -117,10 +117,10 @@ class ClassifierTrainer:
         if y_map is not None:
             self.y.copy_(y_map)
         g = net.grad
-        _lib.call("dl4ss_cls_head_loss_bwd", _lib.ptr(self.prob), _lib.ptr(self.y), _lib.ptr(self.mean),
-                  _lib.ptr(net.view("Linear.weight")), self.B, 2 * net.H, net.num_labels, self.T, _lib.ptr(self.loss),
-                  _lib.ptr(self.dz), _lib.ptr(net.view("Linear.weight", g)), _lib.ptr(net.view("Linear.bias", g)),
-                  _lib.ptr(self.dmb), _lib.stream_ptr())
+        _lib.call("dl4ss_cls_head_loss_bwd", p=_lib.ptr(self.prob), y=_lib.ptr(self.y), m=_lib.ptr(self.mean),
+                  W=_lib.ptr(net.view("Linear.weight")), B=self.B, D=2 * net.H, C=net.num_labels, T=self.T,
+                  loss=_lib.ptr(self.loss), dz=_lib.ptr(self.dz), dW=_lib.ptr(net.view("Linear.weight", g)),
+                  db=_lib.ptr(net.view("Linear.bias", g)), dOut_bcast=_lib.ptr(self.dmb), stream=_lib.stream_ptr())
         return self.loss
 
     # ------------------------------------------------------------------ backward

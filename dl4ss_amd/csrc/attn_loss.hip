@@ -20,7 +20,6 @@
 // order (bitwise deterministic).  PIT: the COST pass produces the K x K pairwise
 // cost matrix per utterance, `pit_select` picks the lowest-index minimising
 // permutation, the GRAD pass uses it; label order (the reference) = identity.
-#include <cstdlib>
 #include "common.h"
 #include <hip/hip_bf16.h>
 
@@ -303,27 +302,37 @@ int attn_common(int pass, int crm, int B, int K, int T, int F, int E, const floa
                 const float* X, long long x_bstride, const float* Y, long long y_bstride, long long y_kstride,
                 const int* perm, float s1, float s2, float* dPre, void* dPre_bf16, long long dpre_bf16_ld,
                 float* part_loss, float* part_dq, float* mask_out, float* pred_out, void* stream,
-                const float* gext = nullptr);
-
+                const float* gext = nullptr) {
+  DL4SS_REQUIRE(B > 0 && K >= 1 && K <= 3 && T > 0 && F > 0 && q && X && Y && part_loss);
+  DL4SS_REQUIRE(pass == 0 || ((dPre || dPre_bf16) && part_dq));
+  DL4SS_REQUIRE(!dPre_bf16 || (E % 2 == 0 && dpre_bf16_ld % 2 == 0 && dpre_bf16_ld >= (long long)F * E &&
+                               ((uintptr_t)dPre_bf16 & 3) == 0));
+  AttnArgs a{};
+  a.B = B; a.T = T; a.F = F; a.rows_per_b = T * F; a.nblk = dl4ss_attn_nblk(T, F);
+  a.V = V; a.Vb = reinterpret_cast<const unsigned short*>(Vb);
+  a.q = q; a.X = X; a.xs = x_bstride; a.Y = Y; a.ys = y_bstride; a.yks = y_kstride;
+  a.perm = perm; a.s1 = s1; a.s2 = s2; a.dPre = dPre; a.part_loss = part_loss; a.part_dq = part_dq;
+  a.dPreB = reinterpret_cast<unsigned*>(dPre_bf16); a.ldpb = dpre_bf16_ld;
+  a.mask_out = mask_out; a.pred_out = pred_out;
+  if (gext)
+    return Vb ? dispatch_adv<true>(E, K, a, gext, as_stream(stream))
+              : dispatch_adv<false>(E, K, a, gext, as_stream(stream));
+  return Vb ? dispatch_v<true>(E, K, crm, pass == 1, a, as_stream(stream))
+            : dispatch_v<false>(E, K, crm, pass == 1, a, as_stream(stream));
+}
 }  // namespace
 
 DL4SS_API int dl4ss_attn_nblk(int T, int F) {
-  // DL4SS_ATTN_TILES tiles per block (default 4: with attn_q4_kernel at C2 -- 32 x 32 blocks, one
-  // round at 4 resident per CU -- GRAD 65.8 / 66.7 / 71.1 us at 4 / 2 / 3 tiles, COST + PIT select
-  // 25.2 / 25.8 / 27.1 us, profiles/r03_attn_q4.jsonl; round 2's attn_kernel preferred 3)
-  static const int tpb = std::getenv("DL4SS_ATTN_TILES") ? std::atoi(std::getenv("DL4SS_ATTN_TILES")) : 4;
+  // 4 tiles per block: with attn_q4_kernel at C2 -- 32 x 32 blocks, one round at 4 resident per CU --
+  // GRAD 65.8 / 66.7 / 71.1 us at 4 / 2 / 3 tiles, COST + PIT select 25.2 / 25.8 / 27.1 us
+  // (profiles/r03_attn_q4.jsonl; round 2's attn_kernel preferred 3)
+  constexpr int tpb = 4;
   const int rows = T * F;
   int nblk = (rows + tpb * TILE - 1) / (tpb * TILE);
   return nblk < 1 ? 1 : nblk;
 }
 
 // pass: 0 = COST (costs / masks only), 1 = GRAD (costs + dPre + dq partials)
-DL4SS_API int dl4ss_mask_attn_loss_ex(int pass, int crm, int B, int K, int T, int F, int E, const float* V,
-                                      const float* q, const float* X, long long x_bstride, const float* Y,
-                                      long long y_bstride, long long y_kstride, const int* perm, float s1, float s2,
-                                      float* dPre, void* dPre_bf16, long long dpre_bf16_ld, float* part_loss,
-                                      float* part_dq, float* mask_out, float* pred_out, void* stream);
-
 DL4SS_API int dl4ss_mask_attn_loss(int pass, int crm, int B, int K, int T, int F, int E, const float* V,
                                    const float* q, const float* X, long long x_bstride, const float* Y,
                                    long long y_bstride, long long y_kstride, const int* perm, float s1, float s2,
@@ -380,31 +389,6 @@ DL4SS_API int dl4ss_mask_attn_loss_adv_bf16v(int B, int K, int T, int F, int E, 
   return attn_common(1, 0, B, K, T, F, E, nullptr, V_bf16, q, X, x_bstride, Y, y_bstride, y_kstride, perm, s1, s2,
                      dPre, dPre_bf16, dpre_bf16_ld, part_loss, part_dq, mask_out, pred_out, stream, dpred_extra);
 }
-
-namespace {
-int attn_common(int pass, int crm, int B, int K, int T, int F, int E, const float* V, const void* Vb, const float* q,
-                const float* X, long long x_bstride, const float* Y, long long y_bstride, long long y_kstride,
-                const int* perm, float s1, float s2, float* dPre, void* dPre_bf16, long long dpre_bf16_ld,
-                float* part_loss, float* part_dq, float* mask_out, float* pred_out, void* stream,
-                const float* gext) {
-  DL4SS_REQUIRE(B > 0 && K >= 1 && K <= 3 && T > 0 && F > 0 && q && X && Y && part_loss);
-  DL4SS_REQUIRE(pass == 0 || ((dPre || dPre_bf16) && part_dq));
-  DL4SS_REQUIRE(!dPre_bf16 || (E % 2 == 0 && dpre_bf16_ld % 2 == 0 && dpre_bf16_ld >= (long long)F * E &&
-                               ((uintptr_t)dPre_bf16 & 3) == 0));
-  AttnArgs a{};
-  a.B = B; a.T = T; a.F = F; a.rows_per_b = T * F; a.nblk = dl4ss_attn_nblk(T, F);
-  a.V = V; a.Vb = reinterpret_cast<const unsigned short*>(Vb);
-  a.q = q; a.X = X; a.xs = x_bstride; a.Y = Y; a.ys = y_bstride; a.yks = y_kstride;
-  a.perm = perm; a.s1 = s1; a.s2 = s2; a.dPre = dPre; a.part_loss = part_loss; a.part_dq = part_dq;
-  a.dPreB = reinterpret_cast<unsigned*>(dPre_bf16); a.ldpb = dpre_bf16_ld;
-  a.mask_out = mask_out; a.pred_out = pred_out;
-  if (gext)
-    return Vb ? dispatch_adv<true>(E, K, a, gext, as_stream(stream))
-              : dispatch_adv<false>(E, K, a, gext, as_stream(stream));
-  return Vb ? dispatch_v<true>(E, K, crm, pass == 1, a, as_stream(stream))
-            : dispatch_v<false>(E, K, crm, pass == 1, a, as_stream(stream));
-}
-}  // namespace
 
 DL4SS_API int dl4ss_pit_select(const float* part_loss, int B, int K, int nblk, int* perm, void* stream) {
   DL4SS_REQUIRE(part_loss && perm && B > 0 && K >= 1 && K <= 3);

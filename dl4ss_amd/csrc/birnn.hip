@@ -2,17 +2,13 @@
 // ABI (include/dl4ss_hip.h).  The kernels and their launch selection are in birnn_fwd.hip,
 // birnn_fwd_pk.hip, birnn_bwd.hip and birnn_bwd_pk.hip; the design is described in birnn_common.h,
 // the LDS and workspace layouts in birnn_layout.h.
-#include <cstdlib>
 #include "birnn_common.h"
 
 using namespace dl4ss_rnn;
 
 namespace {
 
-constexpr int DL4SS_RNN_WS_ZEROED = 0x100;  // precision flag: workspace already zero (no memset)
-constexpr int DL4SS_RNN_DEFER_BIAS = 0x400;  // BPTT: leave the per-row bias partials for dl4ss_birnn_bias_reduce
-constexpr int DL4SS_RNN_DGH_PAD8 = 0x200;  // precision flag (bwd): dGh_bf16 direction stride padded to 8
-constexpr int DL4SS_RNN_DOUT_SLABS_MASK = 0x3000;  // precision field (bwd): dOut = (S - 1) << 12 split-K slabs
+// (the precision flags DL4SS_RNN_WS_ZEROED / _DGH_PAD8 / _DEFER_BIAS / _DOUT_SLABS are the public header's)
 constexpr unsigned SPIN_LIMIT = 1u << 20;  // ~1 s of polling: a stuck hand-off exits, never hangs
 
 struct Plan {
@@ -48,12 +44,10 @@ struct Plan {
 // Co-residency budget of one persistent launch (both directions, all batch chunks): every
 // workgroup must be resident at once, so the plan keeps 2 * nchunk * NG within the device's
 // CU count minus 1/16 of it (240 of 256 on a full MI355X; 30 on a 32-CU CPX partition),
-// leaving room for concurrent kernels (RCCL).  DL4SS_RNN_MAX_WG overrides it (experiments).
+// leaving room for concurrent kernels (RCCL).
 int g_max_wg = 0;  // dl4ss_debug_set_rnn_max_wg (tests force the wider batch chunks)
 int wg_limit() {
   if (g_max_wg > 0) return g_max_wg;
-  static const int env = std::getenv("DL4SS_RNN_MAX_WG") ? std::atoi(std::getenv("DL4SS_RNN_MAX_WG")) : 0;
-  if (env > 0) return env;
   const int cu = device_cu_count();
   return cu > 0 ? cu - cu / 16 : 240;
 }
@@ -84,10 +78,7 @@ bool make_plan(int cell, int B, int H, Plan& p, bool mf = true, int max_wg = 0) 
     const int NG = (H + J - 1) / J;
     if (J > 20) continue;  // gather/publish offset arrays are sized for J <= 20, H <= HMAX(_L)
     int BC = 0;
-    // DL4SS_RNN_MIN_BC (experiments): a wider batch chunk per group, fewer workgroups
-    static const int min_bc = std::getenv("DL4SS_RNN_MIN_BC") ? std::atoi(std::getenv("DL4SS_RNN_MIN_BC")) : 1;
     for (int bc : {1, 2, 4, 8}) {
-      if (bc < min_bc) continue;
       const int nchunk = (B + bc - 1) / bc;
       if (2 * nchunk * NG <= max_wg && bc * J <= NROLE) {
         BC = bc;

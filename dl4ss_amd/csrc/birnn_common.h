@@ -50,7 +50,7 @@
 
 namespace dl4ss_rnn __attribute__((visibility("hidden"))) {
 
-enum { CELL_LSTM = 0, CELL_GRU = 1 };
+enum { CELL_LSTM = DL4SS_CELL_LSTM, CELL_GRU = DL4SS_CELL_GRU };
 
 typedef unsigned long long u64;
 

@@ -3,6 +3,13 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+// The public header is the one declaration of the C ABI: every translation unit sees every prototype, so a
+// DL4SS_API definition whose parameter list or return type differs from its prototype does not compile.
+// (The prototypes carry no visibility attribute; the one on the definition is what exports the symbol.)
+// Included relative to this file, so a compile line that knows only csrc/ (the sanitizer tests, a variant
+// build) needs no further include path.
+#include "../../include/dl4ss_hip.h"
+
 #define DL4SS_API extern "C" __attribute__((visibility("default")))
 
 // Timing-experiment macros that drop stores (results wrong) are accepted only in the experiment

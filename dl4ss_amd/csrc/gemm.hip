@@ -31,8 +31,8 @@ constexpr int NT = 256;
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef short bf16x8 __attribute__((ext_vector_type(8)));
 
-enum { EPI_NONE = 0, EPI_TANH = 1 };
-enum { PREC_F32 = 0, PREC_BF16 = 1 };
+enum { EPI_NONE = DL4SS_EPI_NONE, EPI_TANH = DL4SS_EPI_TANH };
+enum { PREC_F32 = DL4SS_PREC_F32, PREC_BF16 = DL4SS_PREC_BF16 };
 // where gemm_kernel's accumulator tile goes: C (bias, beta, epilogue), atomically onto C, or
 // plainly into slab blockIdx.z of the split-K workspace (no bias, no beta, no epilogue)
 enum { OUT_STORE = 0, OUT_ATOMIC = 1, OUT_SLAB = 2 };

@@ -64,7 +64,8 @@ struct Cfg {
                              : SMEM * 2 <= 80 * 1024 ? 2 : 1;  // workgroups per CU
   static_assert(CPW_A >= 1 && CPW_B >= 1, "at least one DMA per wave and operand");
 };
-enum { EPI_NONE = 0, EPI_TANH = 1, EPI_TANH_BF16 = 2, EPI_SPLIT_SLABS = 3 };
+enum { EPI_NONE = DL4SS_EPI_NONE, EPI_TANH = DL4SS_EPI_TANH, EPI_TANH_BF16 = DL4SS_EPI_TANH_BF16,
+       EPI_SPLIT_SLABS = DL4SS_EPI_SPLIT_SLABS };
 
 // 64 zero bytes every out-of-range k chunk is loaded from (16 B per lane)
 __device__ __attribute__((aligned(64))) const unsigned g_zero_line[16] = {0};

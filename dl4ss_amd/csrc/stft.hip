@@ -29,7 +29,9 @@ constexpr int FPW = 16;             // frames per workgroup
 constexpr int SPAN = HOPL * FPW + NFFT;  // 2304 samples
 constexpr int YS = 17;              // padded row stride (complex) of the transpose
 
-enum { F_COMPLEX = 1, F_MAG = 2, F_LOGMAG = 4, F_CONJ = 8, F_APPLY_MAG = 16, F_APPLY_CRM = 32 };
+// the ABI's flags (include/dl4ss_hip.h) and, above them, the two internal modes of dl4ss_istft_apply
+enum { F_COMPLEX = DL4SS_STFT_COMPLEX, F_MAG = DL4SS_STFT_MAG, F_LOGMAG = DL4SS_STFT_LOGMAG, F_CONJ = DL4SS_STFT_CONJ,
+       F_APPLY_MAG = 16, F_APPLY_CRM = 32 };
 
 // cos / sin of 2*pi*m/16
 __device__ constexpr float C16[16] = {1.0f, 0.92387953251128674f, 0.70710678118654752f, 0.38268343236508977f,

@@ -383,10 +383,9 @@ class SepTrainer:
             return
         wadj = net.view("adj.layer.weight") if net.adjust else None
         # (bf16: the time mean is already in self.mean, the query kernel reads no layer output)
-        _lib.call("dl4ss_query_fwd", None if bf16v else _lib.ptr(self.out[-1]), B, T, 2 * H, _lib.ptr(self.spk),
-                  _lib.ptr(net.view("emb.layer.weight")), _lib.ptr(wadj), self.K, net.W, _lib.ptr(self.q),
-                  _lib.ptr(self.mean), _lib.stream_ptr())
-
+        _lib.call("dl4ss_query_fwd", h=None if bf16v else _lib.ptr(self.out[-1]), B=B, T=T, D=2 * H,
+                  idx=_lib.ptr(self.spk), emb=_lib.ptr(net.view("emb.layer.weight")), w_adj=_lib.ptr(wadj), K=self.K,
+                  W=net.W, q=_lib.ptr(self.q), mean_out=_lib.ptr(self.mean), stream=_lib.stream_ptr())
 
     def _attn_args(self):
         B, K, T, F = self.B, self.K, self.T, self.F
@@ -399,37 +398,32 @@ class SepTrainer:
         """One pass of the fused attention + loss kernels.  ``gext`` (GRAD pass of an adversarial step): a
         second gradient at the prediction, (B, K, T, F) -- the adversarial form of the same kernel."""
         X, xs, Y, ys, yks = self._attn_args()
-        grad = pass_ == 1
-        if gext is not None:
-            bf16v = self.fast and not self.split
-            fn, v = ("dl4ss_mask_attn_loss_adv_bf16v", self.Vb) if bf16v else ("dl4ss_mask_attn_loss_adv", self.V)
-            _lib.call(fn, self.B, self.K, self.T, self.F, self.net.E, _lib.ptr(v), _lib.ptr(self.q), _lib.ptr(X), xs,
-                      _lib.ptr(Y), ys, yks, _lib.ptr(perm), self.s1, self.s2, _lib.ptr(gext),
-                      None if self.fast else _lib.ptr(self.V), _lib.ptr(self.dPreb) if self.fast else None,
-                      self.dPreb.stride(0) if self.fast else 0, _lib.ptr(self.part_loss), _lib.ptr(self.part_dq),
-                      _lib.ptr(mask_out), _lib.ptr(pred_out), _lib.stream_ptr())
-            return
-        if self.align:
+        grad, ptr = pass_ == 1, _lib.ptr
+        # what the four entry points share, by the header's parameter names
+        kw = dict(B=self.B, K=self.K, T=self.T, F=self.F, E=self.net.E, q=ptr(self.q), X=ptr(X), x_bstride=xs,
+                  Y=ptr(Y), y_bstride=ys, y_kstride=yks, perm=ptr(perm), s1=self.s1, s2=self.s2,
+                  part_loss=ptr(self.part_loss), mask_out=ptr(mask_out), pred_out=ptr(pred_out),
+                  stream=_lib.stream_ptr())
+        if self.align and gext is None:
             net = self.net
-            _lib.call("dl4ss_mask_attn_align_loss", pass_, self.B, self.K, self.T, self.F, net.E, _lib.ptr(self.V),
-                      _lib.ptr(self.q), _lib.ptr(net.view("att.Linear_1.weight")),
-                      _lib.ptr(net.view("att.Linear_2.weight")), _lib.ptr(net.view("att.Linear_3.weight")),
-                      _lib.ptr(X), xs, _lib.ptr(Y), ys, yks, _lib.ptr(perm), self.s1, self.s2,
-                      _lib.ptr(self.V) if grad else None, _lib.ptr(self.part_loss),
-                      _lib.ptr(self.part_att) if grad else None, self.part_att.numel(), _lib.ptr(mask_out),
-                      _lib.ptr(pred_out), _lib.stream_ptr())
+            _lib.call("dl4ss_mask_attn_align_loss", pass_=pass_, V=ptr(self.V),
+                      W1=ptr(net.view("att.Linear_1.weight")), W2=ptr(net.view("att.Linear_2.weight")),
+                      w3=ptr(net.view("att.Linear_3.weight")), dPre=ptr(self.V) if grad else None,
+                      part=ptr(self.part_att) if grad else None, part_floats=self.part_att.numel(), **kw)
             return
-        dpre = _lib.ptr(self.V) if grad and not self.fast else None
-        # (the COST pass gets dPre_bf16 too: it selects the same attention kernel as the GRAD pass)
-        dpreb = _lib.ptr(self.dPreb) if self.fast else None
         # bf16 path: V itself is bf16 (the Linear's EPI_TANH_BF16 epilogue); bf16s: fp32 V, bf16 dPre
         bf16v = self.fast and not self.split
-        fn, v = ("dl4ss_mask_attn_loss_bf16v", self.Vb) if bf16v else ("dl4ss_mask_attn_loss_ex", self.V)
-        _lib.call(fn, pass_, int(self.mode == "crm"), self.B, self.K, self.T, self.F,
-                  self.net.E, _lib.ptr(v), _lib.ptr(self.q), _lib.ptr(X), xs, _lib.ptr(Y), ys, yks,
-                  _lib.ptr(perm), self.s1, self.s2, dpre, dpreb, self.dPreb.stride(0) if self.fast else 0,
-                  _lib.ptr(self.part_loss), _lib.ptr(self.part_dq) if grad else None, _lib.ptr(mask_out),
-                  _lib.ptr(pred_out), _lib.stream_ptr())
+        kw["V_bf16" if bf16v else "V"] = ptr(self.Vb if bf16v else self.V)
+        # (the COST pass gets dPre_bf16 too: it selects the same attention kernel as the GRAD pass)
+        kw.update(dPre_bf16=ptr(self.dPreb) if self.fast else None,
+                  dpre_bf16_ld=self.dPreb.stride(0) if self.fast else 0)
+        if gext is not None:
+            _lib.call("dl4ss_mask_attn_loss_adv_bf16v" if bf16v else "dl4ss_mask_attn_loss_adv", dpred_extra=ptr(gext),
+                      dPre=None if self.fast else ptr(self.V), part_dq=ptr(self.part_dq), **kw)
+            return
+        _lib.call("dl4ss_mask_attn_loss_bf16v" if bf16v else "dl4ss_mask_attn_loss_ex", pass_=pass_,
+                  crm=int(self.mode == "crm"), dPre=ptr(self.V) if grad and not self.fast else None,
+                  part_dq=ptr(self.part_dq) if grad else None, **kw)
 
     def loss_and_grad(self):
         """Fused attention + loss + dPre (in place over V) + dq; returns loss (device)."""
@@ -449,15 +443,19 @@ class SepTrainer:
             # partials, straight into their views of the flat gradient (backward_early zeroes only the
             # range in front of them)
             net, g = self.net, self.net.grad
-            _lib.call("dl4ss_loss_finalize", _lib.ptr(self.part_loss), self.B, self.K, self.nblk, _lib.ptr(perm),
-                      self.s1, self.s2, _lib.ptr(self.loss), None, net.W, None, st)
-            _lib.call("dl4ss_attn_align_finalize", _lib.ptr(self.part_att), self.part_att.numel(), self.B, self.K,
-                      self.T, self.F, _lib.ptr(self.q), _lib.ptr(net.view("att.Linear_2.weight")), _lib.ptr(self.dq),
-                      _lib.ptr(net.view("att.Linear_1.weight", g)), _lib.ptr(net.view("att.Linear_2.weight", g)),
-                      _lib.ptr(net.view("att.Linear_3.weight", g)), st)
+            _lib.call("dl4ss_loss_finalize", part_loss=_lib.ptr(self.part_loss), B=self.B, K=self.K, nblk=self.nblk,
+                      perm=_lib.ptr(perm), s1=self.s1, s2=self.s2, loss_out=_lib.ptr(self.loss), part_dq=None, qw=net.W,
+                      dq=None, stream=st)
+            _lib.call("dl4ss_attn_align_finalize", part=_lib.ptr(self.part_att), part_floats=self.part_att.numel(),
+                      B=self.B, K=self.K, T=self.T, F=self.F, q=_lib.ptr(self.q),
+                      W2=_lib.ptr(net.view("att.Linear_2.weight")), dq=_lib.ptr(self.dq),
+                      dW1=_lib.ptr(net.view("att.Linear_1.weight", g)),
+                      dW2=_lib.ptr(net.view("att.Linear_2.weight", g)),
+                      dw3=_lib.ptr(net.view("att.Linear_3.weight", g)), stream=st)
             return self.loss
-        _lib.call("dl4ss_loss_finalize", _lib.ptr(self.part_loss), self.B, self.K, self.nblk, _lib.ptr(perm),
-                  self.s1, self.s2, _lib.ptr(self.loss), _lib.ptr(self.part_dq), self.net.W, _lib.ptr(self.dq), st)
+        _lib.call("dl4ss_loss_finalize", part_loss=_lib.ptr(self.part_loss), B=self.B, K=self.K, nblk=self.nblk,
+                  perm=_lib.ptr(perm), s1=self.s1, s2=self.s2, loss_out=_lib.ptr(self.loss),
+                  part_dq=_lib.ptr(self.part_dq), qw=self.net.W, dq=_lib.ptr(self.dq), stream=st)
         return self.loss
 
     # ------------------------------------------------------------------ backward
@@ -689,11 +687,12 @@ class SepTrainer:
             self.vp.backward()
             return
         wadj = net.view("adj.layer.weight") if net.adjust else None
-        _lib.call("dl4ss_query_bwd_ex", _lib.ptr(self.dq), B, T, 2 * H, _lib.ptr(self.spk),
-                  _lib.ptr(net.view("emb.layer.weight")), _lib.ptr(wadj), _lib.ptr(self.mean), self.K, net.W,
-                  _lib.ptr(net.view("emb.layer.weight", g)),
-                  _lib.ptr(net.view("adj.layer.weight", g)) if net.adjust else None,
-                  _lib.ptr(self.dh_bcast) if net.adjust else None, net.num_labels, self._gbeta, _lib.stream_ptr())
+        _lib.call("dl4ss_query_bwd_ex", dq=_lib.ptr(self.dq), B=B, T=T, D=2 * H, idx=_lib.ptr(self.spk),
+                  emb=_lib.ptr(net.view("emb.layer.weight")), w_adj=_lib.ptr(wadj), mean=_lib.ptr(self.mean), K=self.K,
+                  W=net.W, d_emb=_lib.ptr(net.view("emb.layer.weight", g)),
+                  d_wadj=_lib.ptr(net.view("adj.layer.weight", g)) if net.adjust else None,
+                  dh_bcast=_lib.ptr(self.dh_bcast) if net.adjust else None, n_labels=net.num_labels, beta=self._gbeta,
+                  stream=_lib.stream_ptr())
 
     def backward_late(self):
         """The BPTT chain and the recurrent layers' weight / bias gradients, then the status flag."""

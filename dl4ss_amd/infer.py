@@ -167,9 +167,9 @@ class ClassifierForward:
         """Probabilities (into self.prob) and the speaker choice of one recursion step."""
         logits = self.logits_of(feats)
         n_prev = 0 if prev is None else prev.shape[0]
-        _lib.call("dl4ss_classifier_select", _lib.ptr(logits), self.B, self.net.num_labels, float(alpha), int(top_k),
-                  _lib.ptr(prev), n_prev, _lib.ptr(self.prob), _lib.ptr(sort_index), _lib.ptr(chosen),
-                  _lib.stream_ptr())
+        _lib.call("dl4ss_classifier_select", logits=_lib.ptr(logits), B=self.B, N=self.net.num_labels,
+                  alpha=float(alpha), top_k=int(top_k), prev=_lib.ptr(prev), n_prev=n_prev, prob=_lib.ptr(self.prob),
+                  sort_index=_lib.ptr(sort_index), chosen=_lib.ptr(chosen), stream=_lib.stream_ptr())
         return self.prob
 
     def __call__(self, feats):
@@ -266,8 +266,8 @@ class RecursiveExtractor:
     def _gather(self, idx, K, out):
         """out (B, K, E) = emb[idx (B, K)] (zero rows for idx -1): SPEECH_EMBEDDING, GRID.py:208-213."""
         emb = _lib.ptr(self.net.view("emb.layer.weight"))
-        _lib.call("dl4ss_query_fwd", emb, self.B, 1, 1, _lib.ptr(idx), emb, None, K, self.net.E, _lib.ptr(out), None,
-                  _lib.stream_ptr())
+        _lib.call("dl4ss_query_fwd", h=emb, B=self.B, T=1, D=1, idx=_lib.ptr(idx), emb=emb, w_adj=None, K=K,
+                  W=self.net.E, q=_lib.ptr(out), mean_out=None, stream=_lib.stream_ptr())
 
     def _attend(self, V, q, out):
         """out[b, k] = sigmoid(V[b] . q[b, k]) for q (B, K, E), out (B, K, T, F) contiguous: K launches
@@ -276,8 +276,9 @@ class RecursiveExtractor:
         K = q.shape[1]
         assert q.is_contiguous() and out.is_contiguous() and out.numel() == self.B * K * R
         for k in range(K):
-            _lib.call("dl4ss_attn_dot_fwd_ex", _lib.ptr(V), ctypes.c_void_p(q.data_ptr() + 4 * k * E), K * E, self.B,
-                      R, E, 0, ctypes.c_void_p(out.data_ptr() + 4 * k * R), K * R, _lib.stream_ptr())
+            _lib.call("dl4ss_attn_dot_fwd_ex", V=_lib.ptr(V), q=ctypes.c_void_p(q.data_ptr() + 4 * k * E),
+                      q_stride=K * E, Bq=self.B, R=R, E=E, act=0, mask=ctypes.c_void_p(out.data_ptr() + 4 * k * R),
+                      mask_stride=K * R, stream=_lib.stream_ptr())
 
     def run(self, feats):
         """feats (B, T, F) fp32 on the device (magnitude spectrogram of the mixtures).
@@ -361,11 +362,13 @@ class EnrolledExtractor:
             qk = ctypes.c_void_p(q.data_ptr() + 4 * k * E)
             mk = ctypes.c_void_p(self.masks.data_ptr() + 4 * k * R)
             if self.align:
-                _lib.call("dl4ss_attn_align_fwd", _lib.ptr(V), qk, K * E, _lib.ptr(net.view("att.Linear_1.weight")),
-                          _lib.ptr(net.view("att.Linear_2.weight")), _lib.ptr(net.view("att.Linear_3.weight")), B, R, E,
-                          mk, K * R, _lib.stream_ptr())
+                _lib.call("dl4ss_attn_align_fwd", V=_lib.ptr(V), q=qk, q_stride=K * E,
+                          W1=_lib.ptr(net.view("att.Linear_1.weight")), W2=_lib.ptr(net.view("att.Linear_2.weight")),
+                          w3=_lib.ptr(net.view("att.Linear_3.weight")), Bq=B, R=R, E=E, mask=mk, mask_stride=K * R,
+                          stream=_lib.stream_ptr())
             else:
-                _lib.call("dl4ss_attn_dot_fwd_ex", _lib.ptr(V), qk, K * E, B, R, E, 0, mk, K * R, _lib.stream_ptr())
+                _lib.call("dl4ss_attn_dot_fwd_ex", V=_lib.ptr(V), q=qk, q_stride=K * E, Bq=B, R=R, E=E, act=0, mask=mk,
+                          mask_stride=K * R, stream=_lib.stream_ptr())
         self.mask_net.stack.check()
         return self.masks
 

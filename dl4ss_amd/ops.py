@@ -1,4 +1,6 @@
-"""Torch-tensor wrappers over the C ABI (device memory / streams are torch's).
+"""Torch-tensor wrappers over the C ABI (device memory / streams are torch's).  The ABI's constants (STFT_*, EPI_*,
+PREC, CELLS, the recurrence flags) take their values from the header through ``_lib.CONSTANTS``; a call to an entry
+point of ten or more parameters names every one of them (``_lib.bind`` puts them in the prototype's order).
 
 Each wrapper validates shapes on the host (so a kernel never sees a shape it
 does not assume), allocates outputs with torch and enqueues exactly one C-ABI
@@ -8,7 +10,8 @@ import torch
 
 from . import _lib
 
-STFT_COMPLEX, STFT_MAG, STFT_LOGMAG, STFT_CONJ = 1, 2, 4, 8
+_C = _lib.CONSTANTS  # the enums and flag macros of include/dl4ss_hip.h
+STFT_COMPLEX, STFT_MAG, STFT_LOGMAG, STFT_CONJ = (_C["DL4SS_STFT_" + n] for n in ("COMPLEX", "MAG", "LOGMAG", "CONJ"))
 N_FFT, HOP = 256, 128
 F_BINS = N_FFT // 2 + 1
 
@@ -47,9 +50,9 @@ def stft(x, complex_out=True, mag_out=True, log=False, conj=False, out_c=None, o
         if not mag_out or out_bf16.dtype != torch.bfloat16 or out_bf16.stride(-1) != 1 or \
                 out_bf16.shape[0] < n_bf16 * T or out_bf16.stride(0) < F_BINS or n_bf16 > n_sig:
             raise RuntimeError("stft: out_bf16 must be bf16 rows (>= n_bf16 * T, row stride >= 129) of a magnitude")
-        _lib.call("dl4ss_stft_fwd_ex", _lib.ptr(x), n_sig, N, N_FFT, HOP, flags,
-                  _lib.ptr(out_c) if complex_out else None, _lib.ptr(out_mag), _lib.ptr(out_bf16),
-                  out_bf16.stride(0), n_bf16, _lib.stream_ptr())
+        _lib.call("dl4ss_stft_fwd_ex", x=_lib.ptr(x), n_sig=n_sig, n_samples=N, n_fft=N_FFT, hop=HOP, flags=flags,
+                  X_c64=_lib.ptr(out_c) if complex_out else None, mag=_lib.ptr(out_mag), mag_bf16=_lib.ptr(out_bf16),
+                  ld_bf16=out_bf16.stride(0), n_sig_bf16=n_bf16, stream=_lib.stream_ptr())
         return out_c, out_mag
     _lib.call("dl4ss_stft_fwd", _lib.ptr(x), n_sig, N, N_FFT, HOP, flags, _lib.ptr(out_c) if complex_out else None,
               _lib.ptr(out_mag) if mag_out else None, _lib.stream_ptr())
@@ -94,19 +97,20 @@ def mix_sources(raw, gains, out_src=None, out_mix=None, stats_ws=None, lengths=N
     if shifts is not None and (shifts.dtype != torch.int32 or tuple(shifts.shape) != (B, K) or not shifts.is_cuda
                                or not shifts.is_contiguous()):
         raise RuntimeError("mix_sources: shifts must be a contiguous (B, K) int32 CUDA tensor")
-    _lib.call("dl4ss_mix_sources_rot", _lib.ptr(raw), _lib.ptr(lengths), _lib.ptr(shifts), _lib.ptr(gains), B, K, N,
-              _lib.ptr(stats_ws), _lib.ptr(out_src), _lib.ptr(out_mix), _lib.stream_ptr())
+    _lib.call("dl4ss_mix_sources_rot", raw=_lib.ptr(raw), lengths=_lib.ptr(lengths), shifts=_lib.ptr(shifts),
+              gains=_lib.ptr(gains), B=B, K=K, N=N, stats_ws=_lib.ptr(stats_ws), out_src=_lib.ptr(out_src),
+              out_mix=_lib.ptr(out_mix), stream=_lib.stream_ptr())
     return out_src, out_mix
 
 
 # ---------------------------------------------------------------------------
 # dense contractions
 # ---------------------------------------------------------------------------
-PREC = {"fp32": 0, "bf16": 1}
-EPI_NONE, EPI_TANH, EPI_TANH_BF16 = 0, 1, 2  # 2: tanh written as bf16 (gemm_bf16_gl only)
-# gemm_bf16_gl split-K only: leave the fp32 slabs in ws for their consumer (no combine, out not written;
-# DL4SS_EPI_SPLIT_SLABS, include/dl4ss_hip.h)
-EPI_SPLIT_SLABS = 3
+PREC = {"fp32": _C["DL4SS_PREC_F32"], "bf16": _C["DL4SS_PREC_BF16"]}
+# EPI_TANH_BF16: tanh written as bf16 (gemm_bf16_gl only).  EPI_SPLIT_SLABS, gemm_bf16_gl split-K only: leave the
+# fp32 slabs in ws for their consumer (no combine, out not written)
+EPI_NONE, EPI_TANH, EPI_TANH_BF16, EPI_SPLIT_SLABS = (_C["DL4SS_EPI_" + n]
+                                                      for n in ("NONE", "TANH", "TANH_BF16", "SPLIT_SLABS"))
 
 
 def _mat(t, name):
@@ -189,9 +193,10 @@ def gemm(A, B, transA=False, transB=False, bias=None, epilogue=EPI_NONE, beta=0.
             beta = 1.0
         elif splitk > 1 and beta != 1.0:
             splitk = 1
-    _lib.call("dl4ss_gemm", int(transA), int(transB), M, N, K, _lib.ptr(A, True), A.stride(0), _lib.ptr(B, True), B.stride(0),
-              _lib.ptr(out, True), out.stride(0), _lib.ptr(bias), epilogue, float(beta), PREC[precision], int(splitk),
-              _lib.stream_ptr())
+    _lib.call("dl4ss_gemm", transA=int(transA), transB=int(transB), M=M, N=N, K=K, A=_lib.ptr(A, True), lda=A.stride(0),
+              B=_lib.ptr(B, True), ldb=B.stride(0), C=_lib.ptr(out, True), ldc=out.stride(0), bias=_lib.ptr(bias),
+              epilogue=epilogue, beta=float(beta), precision=PREC[precision], splitk=int(splitk),
+              stream=_lib.stream_ptr())
     return out
 
 
@@ -215,9 +220,11 @@ def _gemm_fixed(A, B, transA, transB, M, N, K, bias, epilogue, beta, out, precis
             ws = _fixed_workspace(A.device, nb)
     else:
         ws = None
-    _lib.call("dl4ss_gemm_fixed", int(transA), int(transB), M, N, K, _lib.ptr(A, True), A.stride(0), _lib.ptr(B, True),
-              B.stride(0), _lib.ptr(out, True), out.stride(0), _lib.ptr(bias), epilogue, float(beta), PREC[precision],
-              splitk, _lib.ptr(ws), ws.numel() * ws.element_size() if ws is not None else 0, _lib.stream_ptr())
+    _lib.call("dl4ss_gemm_fixed", transA=int(transA), transB=int(transB), M=M, N=N, K=K, A=_lib.ptr(A, True),
+              lda=A.stride(0), B=_lib.ptr(B, True), ldb=B.stride(0), C=_lib.ptr(out, True), ldc=out.stride(0),
+              bias=_lib.ptr(bias), epilogue=epilogue, beta=float(beta), precision=PREC[precision], splitk=splitk,
+              ws=_lib.ptr(ws), ws_bytes=ws.numel() * ws.element_size() if ws is not None else 0,
+              stream=_lib.stream_ptr())
     return out
 
 
@@ -278,10 +285,11 @@ def gemm_bf16_gl(A, B, transA=False, transB=False, bias=None, epilogue=EPI_NONE,
     if nb > 0 and ws is not None and ws.numel() < nb:
         raise RuntimeError(f"gemm_bf16_gl: workspace of {ws.numel()} bytes < {nb}")
     ws = (ws if ws is not None else _gl_workspace(A.device, nb)) if nb > 0 else None
-    _lib.call("dl4ss_gemm_bf16_gl", int(transA), int(transB), M, N, K, _lib.ptr(A, True), A.stride(0),
-              _lib.ptr(B, True), B.stride(0), _lib.ptr(out, True), out.stride(0), _lib.ptr(bias), epilogue,
-              float(beta), int(splitk), int(batch), int(strideA), int(strideB), int(strideC), _lib.ptr(ws),
-              ws.numel() if ws is not None else 0, _lib.stream_ptr())
+    _lib.call("dl4ss_gemm_bf16_gl", transA=int(transA), transB=int(transB), M=M, N=N, K=K, A=_lib.ptr(A, True),
+              lda=A.stride(0), B=_lib.ptr(B, True), ldb=B.stride(0), C=_lib.ptr(out, True), ldc=out.stride(0),
+              bias=_lib.ptr(bias), epilogue=epilogue, beta=float(beta), splitk=int(splitk), batch=int(batch),
+              strideA=int(strideA), strideB=int(strideB), strideC=int(strideC), ws=_lib.ptr(ws),
+              ws_bytes=ws.numel() if ws is not None else 0, stream=_lib.stream_ptr())
     return out
 
 
@@ -374,14 +382,14 @@ class GroupedGemm:
             c.zero_() if beta == 0.0 else c.mul_(beta)  # beta 0: C is not read (stale NaN included)
         if self.n == 0:
             return
+        group = dict(n=self.n, transA=self.ta, transB=self.tb, M=self.M, N=self.N, K=self.K, A=self.A, lda=self.lda,
+                     B=self.B, ldb=self.ldb, C=self.C, ldc=self.ldc, beta=self.beta, splitk=self.splitk,
+                     ws=_lib.ptr(self.ws), ws_bytes=self.ws.numel(), stream=_lib.stream_ptr())
         if self.grid > 0 or self.cfg != 1 or self.rowsum is not None:
-            _lib.call("dl4ss_gemm_bf16_gl_grouped_ex", self.n, self.ta, self.tb, self.M, self.N, self.K, self.A, self.lda,
-                      self.B, self.ldb, self.C, self.ldc, self.beta, self.splitk, _lib.ptr(self.ws), self.ws.numel(),
-                      self.grid, self.cfg, self.one_per_cu, self.rowsum, _lib.stream_ptr())
+            _lib.call("dl4ss_gemm_bf16_gl_grouped_ex", grid=self.grid, cfg=self.cfg, one_per_cu=self.one_per_cu,
+                      rowsum=self.rowsum, **group)
             return
-        _lib.call("dl4ss_gemm_bf16_gl_grouped", self.n, self.ta, self.tb, self.M, self.N, self.K, self.A, self.lda,
-                  self.B, self.ldb, self.C, self.ldc, self.beta, self.splitk, _lib.ptr(self.ws), self.ws.numel(),
-                  _lib.stream_ptr())
+        _lib.call("dl4ss_gemm_bf16_gl_grouped", **group)
 
 
 def to_bf16(x, out=None):
@@ -457,20 +465,21 @@ def adam_(p, g, m, v, step, lr=2e-4, betas=(0.9, 0.999), eps=1e-8, status=None, 
             raise ValueError("adam_: gnorm must hold 2 float32 values")
         if nonfinite.dtype != torch.int32 or nonfinite.numel() < 1:
             raise ValueError("adam_: nonfinite must be an int32 counter")
-        sh = shadow if shadow is not None else (0, None, None, None, None, None)
-        _lib.call("dl4ss_adam_clipped", _lib.ptr(p), _lib.ptr(g), _lib.ptr(m), _lib.ptr(v), p.numel(),
-                  float(lr), float(betas[0]), float(betas[1]), float(eps), int(step), _lib.ptr(status),
-                  _lib.ptr(dp_flag), float(gscale), _lib.ptr(loss), *sh, _lib.ptr(part), n_part, max_norm,
-                  _lib.ptr(gnorm), _lib.ptr(nonfinite), _lib.stream_ptr())
-        return
-    if shadow is not None:
-        _lib.call("dl4ss_adam_guarded_dp_scaled_bf16", _lib.ptr(p), _lib.ptr(g), _lib.ptr(m), _lib.ptr(v), p.numel(),
-                  float(lr), float(betas[0]), float(betas[1]), float(eps), int(step), _lib.ptr(status),
-                  _lib.ptr(dp_flag), float(gscale), _lib.ptr(loss), *shadow, _lib.stream_ptr())
-        return
-    _lib.call("dl4ss_adam_guarded_dp_scaled", _lib.ptr(p), _lib.ptr(g), _lib.ptr(m), _lib.ptr(v), p.numel(),
-              float(lr), float(betas[0]), float(betas[1]), float(eps), int(step), _lib.ptr(status), _lib.ptr(dp_flag),
-              float(gscale), _lib.ptr(loss), _lib.stream_ptr())
+    # the parameters the three entry points share, then the shadow segments (none: nseg 0), then the clip's
+    step_kw = dict(p=_lib.ptr(p), g=_lib.ptr(g), m=_lib.ptr(m), v=_lib.ptr(v), n=p.numel(), lr=float(lr),
+                   beta1=float(betas[0]), beta2=float(betas[1]), eps=float(eps), step=int(step),
+                   status=_lib.ptr(status), dp_flag=_lib.ptr(dp_flag), gscale=float(gscale), loss=_lib.ptr(loss),
+                   stream=_lib.stream_ptr())
+    if clip is not None or shadow is not None:
+        nseg, seg_off, seg_rows, seg_cols, seg_y, seg_ldy = shadow if shadow is not None else (0,) + (None,) * 5
+        step_kw.update(nseg=nseg, seg_off=seg_off, seg_rows=seg_rows, seg_cols=seg_cols, seg_y=seg_y, seg_ldy=seg_ldy)
+    if clip is not None:
+        _lib.call("dl4ss_adam_clipped", part=_lib.ptr(part), n_part=n_part, max_norm=max_norm, gnorm=_lib.ptr(gnorm),
+                  nonfinite=_lib.ptr(nonfinite), **step_kw)
+    elif shadow is not None:
+        _lib.call("dl4ss_adam_guarded_dp_scaled_bf16", **step_kw)
+    else:
+        _lib.call("dl4ss_adam_guarded_dp_scaled", **step_kw)
 
 
 # the Discriminator's launch sequences, over the caller's buffers (autograd's Functions, the adversarial step)
@@ -482,8 +491,8 @@ def disc_forward(prec, maps, params, ys, logit, score):
     _lib.call("dl4ss_disc_conv1_fwd", prec, _lib.ptr(maps), w1, b1, N, T, F, _lib.ptr(y1), st)
     for x, y, w, b in ((y1, y2, w2, b2), (y2, y3, w3, b3)):
         _lib.call("dl4ss_disc_conv64_fwd", prec, _lib.ptr(x), w, b, N, x.shape[1], x.shape[2], _lib.ptr(y), st)
-    _lib.call("dl4ss_disc_head_fwd", prec, _lib.ptr(y3), wf, bf, N, y3.shape[1], y3.shape[2], _lib.ptr(logit),
-              _lib.ptr(score), st)
+    _lib.call("dl4ss_disc_head_fwd", prec=prec, y3=_lib.ptr(y3), wf=wf, bf=bf, N=N, H3=y3.shape[1], W3=y3.shape[2],
+              z=_lib.ptr(logit), score=_lib.ptr(score), stream=st)
 
 
 def disc_backward(prec, maps, weights, ys, dys, score, dscore, target, loss, dz, grads, dx, ws, ws_bytes):
@@ -493,23 +502,24 @@ def disc_backward(prec, maps, weights, ys, dys, score, dscore, target, loss, dz,
     w1, w2, w3, wf = (_lib.ptr(w) for w in weights)
     dw1, db1, dw2, db2, dw3, db3, dwf, dbf = (_lib.ptr(g) for g in grads)
     (N, T, F), (y1, y2, y3), (d1, d2, d3), ws, st = maps.shape, ys, dys, _lib.ptr(ws), _lib.stream_ptr()
-    _lib.call("dl4ss_disc_head_bwd", prec, _lib.ptr(y3), wf, _lib.ptr(score), _lib.ptr(dscore), float(target), N,
-              y3.shape[1], y3.shape[2], _lib.ptr(loss), _lib.ptr(dz), dwf, dbf, _lib.ptr(d3), st)
+    _lib.call("dl4ss_disc_head_bwd", prec=prec, y3=_lib.ptr(y3), wf=wf, score=_lib.ptr(score), dscore=_lib.ptr(dscore),
+              target=float(target), N=N, H3=y3.shape[1], W3=y3.shape[2], loss=_lib.ptr(loss), dz=_lib.ptr(dz), dwf=dwf,
+              dbf=dbf, dy3=_lib.ptr(d3), stream=st)
     for x, y, dy, w, dx_, dw, db in ((y2, y3, d3, w3, d2, dw3, db3), (y1, y2, d2, w2, d1, dw2, db2)):
-        _lib.call("dl4ss_disc_conv64_bwd", prec, _lib.ptr(x), _lib.ptr(y), _lib.ptr(dy), w, N, x.shape[1], x.shape[2],
-                  _lib.ptr(dx_), dw, db, ws, ws_bytes, st)
-    _lib.call("dl4ss_disc_conv1_bwd", prec, _lib.ptr(maps), _lib.ptr(y1), _lib.ptr(d1), w1, N, T, F, _lib.ptr(dx), dw1,
-              db1, ws, ws_bytes, st)
+        _lib.call("dl4ss_disc_conv64_bwd", prec=prec, x=_lib.ptr(x), y=_lib.ptr(y), dy=_lib.ptr(dy), w=w, N=N,
+                  Hin=x.shape[1], Win=x.shape[2], dx=_lib.ptr(dx_), dw=dw, db=db, ws=ws, ws_bytes=ws_bytes, stream=st)
+    _lib.call("dl4ss_disc_conv1_bwd", prec=prec, x=_lib.ptr(maps), y1=_lib.ptr(y1), dy1=_lib.ptr(d1), w=w1, N=N, T=T,
+              F=F, dx=_lib.ptr(dx), dw=dw1, db=db1, ws=ws, ws_bytes=ws_bytes, stream=st)
 
 
 # ---------------------------------------------------------------------------
 # the bidirectional recurrence
 # ---------------------------------------------------------------------------
-CELLS ={"lstm": 0, "gru": 1}
+CELLS = {"lstm": _C["DL4SS_CELL_LSTM"], "gru": _C["DL4SS_CELL_GRU"]}
 # flags OR-ed into the recurrence entry points' precision argument (include/dl4ss_hip.h)
-WS_ZEROED = 0x100  # DL4SS_RNN_WS_ZEROED: the caller keeps the hand-off workspace zeroed
-DGH_PAD8 = 0x200  # DL4SS_RNN_DGH_PAD8: each direction's bf16 dGh columns start 16-B aligned
-DEFER_BIAS = 0x400  # DL4SS_RNN_DEFER_BIAS: bias partials stay in the workspace (dl4ss_birnn_bias_reduce)
+WS_ZEROED = _C["DL4SS_RNN_WS_ZEROED"]  # the caller keeps the hand-off workspace zeroed
+DGH_PAD8 = _C["DL4SS_RNN_DGH_PAD8"]  # each direction's bf16 dGh columns start 16-B aligned
+DEFER_BIAS = _C["DL4SS_RNN_DEFER_BIAS"]  # bias partials stay in the workspace (dl4ss_birnn_bias_reduce)
 
 
 def DOUT_SLABS(n):  # DL4SS_RNN_DOUT_SLABS(S): the BPTT sums dOut's S split-K slabs itself
@@ -559,8 +569,8 @@ def pad8(n):
 
 def hilo(x, y, segw, pattern, nseg=3):
     """y = the split image of the fp32 rows x: nseg segments of segw, hi / lo by pattern bits."""
-    _lib.call("dl4ss_f32_to_bf16_hilo", _lib.ptr(x, True), x.stride(0), x.shape[0], x.shape[1], _lib.ptr(y),
-              y.stride(0), segw, nseg, pattern, _lib.stream_ptr())
+    _lib.call("dl4ss_f32_to_bf16_hilo", x=_lib.ptr(x, True), ldx=x.stride(0), rows=x.shape[0], cols=x.shape[1],
+              y=_lib.ptr(y), ldy=y.stride(0), segw=segw, nseg=nseg, pattern=pattern, stream=_lib.stream_ptr())
 
 
 def birnn_plan(cell, B, H, precision="bf16", max_wg=0):
@@ -608,8 +618,9 @@ def vp_compact(x, rule="nonzero", thr=None, lengths=None, xc=None, len_out=None,
     idx = torch.empty(n, T, **i32) if idx is None else _i32c(idx, "vp_compact(idx)", n * T)
     if xc.numel() != x.numel():
         raise RuntimeError("vp_compact: xc must have x's size")
-    _lib.call("dl4ss_vp_compact", _lib.ptr(x), n, T, F, VP_RULES[rule], float(0.0 if thr is None else thr),
-              _lib.ptr(lengths), _lib.ptr(xc), _lib.ptr(len_out), _lib.ptr(idx), _lib.stream_ptr())
+    _lib.call("dl4ss_vp_compact", x=_lib.ptr(x), n=n, T=T, F=F, rule=VP_RULES[rule],
+              thr=float(0.0 if thr is None else thr), len_in=_lib.ptr(lengths), xc=_lib.ptr(xc), len=_lib.ptr(len_out),
+              idx=_lib.ptr(idx), stream=_lib.stream_ptr())
     return xc, len_out, idx
 
 
@@ -623,8 +634,8 @@ def vp_shift(src, dst, lengths, c0, c1, direction, other=0):
         raise RuntimeError("vp_shift: src and dst must be (n, T, ld) of one shape")
     n, T, ld = src.shape
     _i32c(lengths, "vp_shift(lengths)", n)
-    _lib.call("dl4ss_vp_shift", _lib.ptr(src), _lib.ptr(dst), n, T, ld, int(c0), int(c1), _lib.ptr(lengths),
-              int(direction), int(other), _lib.stream_ptr())
+    _lib.call("dl4ss_vp_shift", src=_lib.ptr(src), dst=_lib.ptr(dst), n=n, T=T, ld=ld, c0=int(c0), c1=int(c1),
+              len=_lib.ptr(lengths), dir=int(direction), other=int(other), stream=_lib.stream_ptr())
     return dst
 
 
@@ -708,8 +719,8 @@ def spk_memory_bwd(dq, v, u, ids, mem, dv=None):
     dv = torch.empty_like(v) if dv is None else _f32c(dv, "spk_memory_bwd(dv)")
     if dq.numel() != n * E or u.numel() != n * E or dv.numel() != n * E:
         raise RuntimeError("spk_memory_bwd: dq, u and dv must be (n, E)")
-    _lib.call("dl4ss_spk_memory_bwd", _lib.ptr(dq), _lib.ptr(v), _lib.ptr(u), _lib.ptr(ids), _lib.ptr(mem), n, E, M,
-              _lib.ptr(dv), _lib.stream_ptr())
+    _lib.call("dl4ss_spk_memory_bwd", dq=_lib.ptr(dq), v=_lib.ptr(v), u=_lib.ptr(u), ids=_lib.ptr(ids),
+              mem=_lib.ptr(mem), n=n, E=E, M=M, dv=_lib.ptr(dv), stream=_lib.stream_ptr())
     return dv
 
 

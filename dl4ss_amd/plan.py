@@ -107,7 +107,8 @@ def check_args(net, batch, k, n_samples, mode, precision, rnn_precision, loss_ch
 
 
 # settled A/B knobs (DESIGN.md section 11 keeps their last figures): the default of each is the only path now
-RETIRED_KNOBS = ("DL4SS_DX_SPLIT", "DL4SS_DEFER_BIAS", "DL4SS_SIDE_LATE", "DL4SS_DW_SPLITS", "DL4SS_DW_CFG")
+RETIRED_KNOBS = ("DL4SS_DX_SPLIT", "DL4SS_DEFER_BIAS", "DL4SS_SIDE_LATE", "DL4SS_DW_SPLITS", "DL4SS_DW_CFG") + \
+    _lib.RETIRED_ENV  # (the three the library itself read: _lib._load refuses them for every consumer)
 
 
 def step_plan(net, batch, n_samples, precision, rnn_precision=None, process_group=None):

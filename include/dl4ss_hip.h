@@ -201,6 +201,7 @@ enum { DL4SS_CELL_LSTM = 0, DL4SS_CELL_GRU = 1 };
  * the BPTT sums them per element in slab order from zero (((0 + s0) + s1) + ...), bitwise the combine
  * launch it replaces.  Packed bf16 BPTT at batch chunks of 4 only (hipErrorInvalidValue otherwise). */
 #define DL4SS_RNN_DOUT_SLABS(S) ((((S) - 1) & 3) << 12)
+#define DL4SS_RNN_DOUT_SLABS_MASK 0x3000
 int dl4ss_birnn_bias_reduce(int cell, int B, int H, int n, void* const* workspaces, float* const* db_ih,
                             float* const* db_hh, void* stream);
 /* dl4ss_birnn_bias_reduce with db = beta db + sums: beta 0 writes db_ih / db_hh without reading them
@@ -211,7 +212,7 @@ long long dl4ss_birnn_workspace_bytes(int cell, int B, int H);
 /* The persistent recurrence's plan under a co-residency budget: every workgroup of a launch
  * (2 directions x nchunk batch chunks x NG units groups) must be resident at once, so the
  * batch chunk BC is the smallest in {1, 2, 4, 8} with 2 * nchunk * NG <= max_wg (max_wg <= 0:
- * the current device's CUs minus 1/16, 240 on a full MI355X; env DL4SS_RNN_MAX_WG overrides).
+ * the current device's CUs minus 1/16, 240 on a full MI355X; dl4ss_debug_set_rnn_max_wg overrides).
  * info[5] = {BC, NG, J, nchunk, grid}.  Host-only when max_wg > 0.  0, or
  * hipErrorInvalidValue when no plan fits.  Every launch re-checks the grid against the CU
  * count x the kernel's occupancy and fails with hipErrorCooperativeLaunchTooLarge (720)

@@ -5,7 +5,9 @@ trees can compare.
     python tools/launch_trace.py --compare a.json b.json        print the first difference, or "identical"
     python tools/launch_trace.py --list                         the case names
 
-``_lib.call`` is wrapped (record, then forward).  Integers and floats are recorded verbatim.  Every pointer --
+``_lib.call`` is wrapped (record, then forward); what is recorded is the bound positional tuple (``_lib.bind`` puts
+keyword arguments into the prototype's order; a tree without it calls positionally, and its arguments are taken as
+given), so records of both kinds of tree compare.  Integers and floats are recorded verbatim.  Every pointer --
 also each element of a ctypes pointer array, so the GroupedGemm tables and the conversion / bias-reduce lists --
 becomes (region, byte offset): a region is the torch storage that contains the address, numbered by first
 appearance in the trace; the storages are found after the steps by walking the trainer's and the net's
@@ -186,7 +188,10 @@ def record(case, out, tree):
         tr = engine.SepTrainer(net, B, K, N, **kw)
     trace, call, losses, norms = [], _lib.call, [], []
 
-    def recording_call(name, *args):
+    bind = getattr(_lib, "bind", lambda name, args, kw: args)  # (an older tree: positional calls only)
+
+    def recording_call(name, *args, **kw):
+        args = bind(name, args, kw)
         trace.append((name, [raw(a) for a in args]))
         return call(name, *args)
 
