@@ -1,4 +1,5 @@
-"""ctypes binding of ``libdl4ss_hip.so``, derived from the C ABI's one declaration, ``include/dl4ss_hip.h``.
+"""ctypes binding of ``libdl4ss_hip.so``, derived from the C ABI's one declaration, ``include/dl4ss_hip.h``
+(and ``include/dl4ss_imgq.h``, the image-query encoder's entry points, parsed the same way into ``IMGQ_*`` tables).
 
 The header is parsed once at import: every prototype gives the entry point's ``argtypes`` (``SIGNATURES``), its
 ``restype`` (``RESTYPES``) and its parameter names (``PARAMS``); every enum constant and ``#define DL4SS_* <integer>``
@@ -24,6 +25,7 @@ import torch
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("DL4SS_LIB", os.path.join(_HERE, "libdl4ss_hip.so"))
 HEADER = os.path.join(os.path.dirname(_HERE), "include", "dl4ss_hip.h")
+IMGQ_HEADER = os.path.join(os.path.dirname(_HERE), "include", "dl4ss_imgq.h")  # the image-query encoder's entry points
 
 P = ctypes.c_void_p
 I = ctypes.c_int
@@ -38,48 +40,57 @@ _PROTO = re.compile(r"(int|long long|void)\s+(dl4ss_\w+)\s*\(([^()]*)\)\s*;")
 _INT = r"(0[xX][0-9a-fA-F]+|\d+)"
 
 
-def parse_header(text):
-    """(signatures, restypes, params, constants) of the header ``text``: name -> argtypes list, name -> restype,
-    name -> parameter names, and the integer enum constants and object-like ``DL4SS_*`` macros."""
+def parse_header(text, name="dl4ss_hip.h"):
+    """(signatures, restypes, params, constants) of the header ``text`` (``name``: what an error calls it):
+    entry -> argtypes list, entry -> restype, entry -> parameter names, and the integer enum constants and
+    object-like ``DL4SS_*`` macros."""
     text = re.sub(r"/\*.*?\*/|//[^\n]*", " ", text, flags=re.S)
     sigs, res, params, consts = {}, {}, {}, {}
     for m in re.finditer(r"^(?!\s*#)[^\n]*\bdl4ss_\w+\s*\(", text, flags=re.M):  # every line that opens a prototype
         line = m.group(0).strip()
         proto = _PROTO.match(text, m.start())
         if not proto:
-            raise ValueError(f"dl4ss_hip.h: cannot parse the declaration at {line!r}")
-        ret, name, plist = proto.groups()
+            raise ValueError(f"{name}: cannot parse the declaration at {line!r}")
+        ret, entry, plist = proto.groups()
         argtypes, names = [], []
         for p in plist.split(","):
             words = [w for w in re.findall(r"[A-Za-z_]\w*", re.sub(r"\[\d*\]", "", p)) if w != "const"]
             base, pname = " ".join(words[:-1]), words[-1] if words else ""
             pointer = "*" in p or "[" in p
             if base not in (_POINTEE if pointer else _VALUE) or pname in names:
-                raise ValueError(f"dl4ss_hip.h: cannot classify parameter {p.strip()!r} of {line!r} "
+                raise ValueError(f"{name}: cannot classify parameter {p.strip()!r} of {line!r} "
                                  "(unknown type, no name or a repeated name)")
             argtypes.append(P if pointer else _VALUE[base])
             names.append(pname)
-        sigs[name], res[name], params[name] = argtypes, _RETURN[ret], tuple(names)
+        sigs[entry], res[entry], params[entry] = argtypes, _RETURN[ret], tuple(names)
     for m in re.finditer(r"\benum\b[^;]*;", text):  # anonymous `enum { ... };` only: any other form is refused
         enum = re.fullmatch(r"enum\s*\{([^{}]*)\}\s*;", m.group(0))
         if not enum:
-            raise ValueError(f"dl4ss_hip.h: cannot parse the enum at {m.group(0)[:60]!r}")
+            raise ValueError(f"{name}: cannot parse the enum at {m.group(0)[:60]!r}")
         for item in filter(None, (x.strip() for x in enum.group(1).split(","))):
             m = re.fullmatch(r"(\w+)\s*=\s*" + _INT, item)
             if not m:
-                raise ValueError(f"dl4ss_hip.h: enum constant {item!r} has no integer value")
+                raise ValueError(f"{name}: enum constant {item!r} has no integer value")
             consts[m.group(1)] = int(m.group(2), 0)
     for m in re.finditer(r"^#define[ \t]+(DL4SS_\w+)[ \t]+([^\n]*)$", text, flags=re.M):  # (not function-like)
         if not re.fullmatch(_INT, m.group(2).strip()):
-            raise ValueError(f"dl4ss_hip.h: macro {m.group(0)!r} is not an integer")
+            raise ValueError(f"{name}: macro {m.group(0)!r} is not an integer")
         consts[m.group(1)] = int(m.group(2).strip(), 0)
     return sigs, res, params, consts
 
 
 with open(HEADER) as _f:
     SIGNATURES, RESTYPES, PARAMS, CONSTANTS = parse_header(_f.read())
+# the second public header, in tables of its own: SIGNATURES / RESTYPES / PARAMS / exported_symbols() stay what
+# dl4ss_hip.h declares
+with open(IMGQ_HEADER) as _f:
+    IMGQ_SIGNATURES, IMGQ_RESTYPES, IMGQ_PARAMS, IMGQ_CONSTANTS = parse_header(_f.read(), "dl4ss_imgq.h")
+if set(IMGQ_SIGNATURES) & set(SIGNATURES):
+    raise ValueError(f"dl4ss_imgq.h declares again: {sorted(set(IMGQ_SIGNATURES) & set(SIGNATURES))}")
 # keyword -> slot of every entry point (a header name that is a Python keyword takes a trailing underscore)
-_SLOTS = {name: {p + "_" if keyword.iskeyword(p) else p: i for i, p in enumerate(ps)} for name, ps in PARAMS.items()}
+_SLOTS = {name: {p + "_" if keyword.iskeyword(p) else p: i for i, p in enumerate(ps)}
+          for name, ps in {**PARAMS, **IMGQ_PARAMS}.items()}
+_ALL_PARAMS = {**PARAMS, **IMGQ_PARAMS}
 # knobs the library itself used to read from the environment, retired with plan.RETIRED_KNOBS
 RETIRED_ENV = ("DL4SS_ATTN_TILES", "DL4SS_RNN_MAX_WG", "DL4SS_RNN_MIN_BC")
 
@@ -102,6 +113,14 @@ def _load():
         fn = getattr(lib, name)
         fn.argtypes = argtypes
         fn.restype = RESTYPES[name]
+    # the second header's entry points.  A library without them still loads: the binding tests stand a stub with
+    # the first header's names alone in for the library, and DL4SS_LIB may name a build from before imgq.hip.
+    # Calling one that is missing fails in ctypes' own lookup, with the symbol's name: there is no other path
+    for name, argtypes in IMGQ_SIGNATURES.items():
+        fn = getattr(lib, name, None)
+        if fn is not None:
+            fn.argtypes = argtypes
+            fn.restype = IMGQ_RESTYPES[name]
     hip = ctypes.CDLL("libamdhip64.so")
     hip.hipGetErrorString.restype = ctypes.c_char_p
     hip.hipGetErrorString.argtypes = [ctypes.c_int]
@@ -116,6 +135,10 @@ def lib():
 
 def exported_symbols():
     return list(SIGNATURES)
+
+
+def imgq_exported_symbols():
+    return list(IMGQ_SIGNATURES)
 
 
 def stream_ptr(stream=None):
@@ -141,10 +164,10 @@ def bind(name, args, kw):
     ``TypeError`` unless every parameter of the prototype is given exactly once."""
     slots = _SLOTS.get(name)
     if slots is None:
-        raise TypeError(f"{name} is not declared in include/dl4ss_hip.h")
+        raise TypeError(f"{name} is not declared in include/dl4ss_hip.h or include/dl4ss_imgq.h")
     n, given = len(slots), len(args) + len(kw)
     if len(args) > n:
-        raise TypeError(f"{name} takes {n} arguments (the last is {PARAMS[name][-1]!r}), {given} given")
+        raise TypeError(f"{name} takes {n} arguments (the last is {_ALL_PARAMS[name][-1]!r}), {given} given")
     if not kw and given == n:
         return tuple(args)
     out = list(args) + [None] * (n - len(args))

@@ -160,3 +160,24 @@ def load_voiceprint(path, vnet, memory):
         raise ValueError(f"{path}: mem missing or not of shape {(memory.M, memory.E)}")
     vnet.load_state_dict(sd["voiceprint"])
     memory.load_state_dict(sd["memory"])
+
+
+def save_image_query(path, inet, memory):
+    """The image-query encoder's parameters (``img.*``) and the speaker memory in one file (as save_voiceprint)."""
+    torch.save({"image_query": {k: v.cpu() for k, v in inet.state_dict().items()},
+                "memory": {k: v.cpu() for k, v in memory.state_dict().items()}}, path)
+
+
+def load_image_query(path, inet, memory):
+    """Load a save_image_query file into ``inet`` and ``memory`` (in place; shapes must match)."""
+    sd = torch.load(path, map_location="cpu", weights_only=True)
+    if not isinstance(sd, dict) or set(sd) != {"image_query", "memory"}:
+        raise ValueError(f"{path}: not a save_image_query file")
+    for name, shape in inet.specs:
+        if name not in sd["image_query"] or tuple(sd["image_query"][name].shape) != tuple(shape):
+            raise ValueError(f"{path}: {name} missing or not of shape {tuple(shape)}")
+    mem = sd["memory"].get("mem") if isinstance(sd["memory"], dict) else None
+    if mem is None or tuple(mem.shape) != (memory.M, memory.E):  # before either is written
+        raise ValueError(f"{path}: mem missing or not of shape {(memory.M, memory.E)}")
+    inet.load_state_dict(sd["image_query"])
+    memory.load_state_dict(sd["memory"])

@@ -24,6 +24,7 @@ from .adversarial import AdvStep
 from .ops import CELLS, DEFER_BIAS, DGH_PAD8, DOUT_SLABS, WS_ZEROED, pad8  # noqa: F401 (re-exported)
 from .params import DiscNet, FlatParams, SepNet, _ngate  # noqa: F401 (re-exported)
 from .plan import RETIRED_KNOBS, check_args, step_plan  # noqa: F401 (re-exported)
+from .imagequery import ImageQueryStep
 from .voiceprint import VoiceprintStep
 
 
@@ -45,6 +46,15 @@ class SepTrainer:
     "label", single GPU, eager only; everything else is refused (plan.check_args).  None (the default): no launch is
     added and no line of the step changes.
 
+    ``image_query`` (an ``imagequery.ImageQueryNet``) with ``memory``: the same step with the target named by a
+    picture (Multi_modal/software/DL4SS_Keras/nnet.py:70-94) -- the queries are the image-query CNN over the step's
+    ``images`` (B, K, h, w), given to step(images=), accumulated into and read back from the speaker memory; the
+    encoder trains at ``image_query_lr`` (default ``lr``), ``memory_refresh`` as above.  A step whose loss is not
+    finite is refused on device (no parameter, moment or memory row changes; check() raises).  The refusal is
+    sticky, as a time-out's is: the status word keeps bit 1 and every step enqueued behind it is refused too, until
+    check() has been called.  The voiceprint
+    step's limits (fp32, mode "label", single GPU, eager only) and refusals apply.
+
     ``splitk_reduce`` "fixed" (precision "fp32" only): every backward GEMM of the step splits K through fp32 slabs
     that are added in a fixed order (ops.gemm(reduce="fixed"), one trainer-owned workspace) -- 'align', which runs
     them unsplit otherwise, too -- the bias gradients are fixed-order column sums (ops.vp_colsum), and with
@@ -55,10 +65,12 @@ class SepTrainer:
                  loss_channels=None, betas=(0.9, 0.999), eps=1e-8, process_group=None, rnn_precision=None,
                  adversary=None, adv_weight=1.0, adv_lr=None, disc_adv_update=True, clip_norm=None,
                  adv_clip_norm=None, voiceprint=None, memory=None, voiceprint_lr=None, memory_refresh="reference",
-                 splitk_reduce="atomic"):
+                 splitk_reduce="atomic", image_query=None, image_query_lr=None):
         self.clip_norm, self.adv_clip_norm = check_args(  # every refusal, before any device call
             net, batch, k, n_samples, mode, precision, rnn_precision, loss_channels, process_group, adversary,
-            clip_norm, adv_clip_norm, voiceprint, memory, memory_refresh, splitk_reduce=splitk_reduce)
+            clip_norm, adv_clip_norm, voiceprint, memory, memory_refresh, splitk_reduce=splitk_reduce,
+            inet=image_query)
+        self.inet = image_query
         self.vnet, self.memory, self.memory_refresh, self.adversary = voiceprint, memory, memory_refresh, adversary
         self.align = getattr(net, "attention", "dot") == "align"
         # rnn_precision, fast, split, split_x2, grouped, _ws_fill, dh_split, dh_slabs, xw, xw_kmax, xw_split0, buckets,
@@ -172,6 +184,13 @@ class SepTrainer:
             self.vp = VoiceprintStep(voiceprint, memory, memory_refresh, self.mag_src, self.spk, self.q, self.dq,
                                      self.status, self.loss, lr if voiceprint_lr is None else voiceprint_lr, betas, eps,
                                      wgrad_split="auto" if splitk_reduce == "fixed" else 1)
+            self.vp_enc, self.vp_opt = self.vp.enc, self.vp.opt
+        self.images = None
+        if image_query is not None:  # the same slot: the trainer calls queries / backward / optimizer_step on either
+            self.images = torch.zeros(B, K, image_query.h, image_query.w, **f32)
+            self.vp = ImageQueryStep(image_query, memory, memory_refresh, self.images, self.spk, self.q, self.dq,
+                                     self.status, self.loss, lr if image_query_lr is None else image_query_lr, betas,
+                                     eps)
             self.vp_enc, self.vp_opt = self.vp.enc, self.vp.opt
         if not self.fast:
             return
@@ -812,6 +831,8 @@ class SepTrainer:
         Discriminator's updates run first and are guarded by adv_clip_norm alone: a non-finite separation
         gradient does not undo them."""
         self.wait_allreduce()
+        if self.inet is not None:  # a non-finite loss refuses this step's updates and memory store
+            self.vp.guard()
         if self.adv is not None:  # the Discriminator's updates first (the reference's order)
             self.adv.optimizer_step()
         shadow = self._shadow if (self._shadow_on and hasattr(self, "_shadow")) else None
@@ -825,9 +846,23 @@ class SepTrainer:
         if self.vp is not None:  # the encoder steps with the net's count, then the memory refresh
             self.vp.optimizer_step(self.opt.step_count)
 
-    def step(self, raw, gains, spk_idx, lengths=None):
+    def set_images(self, images):
+        """The step's images (B, K, h, w) into the trainer's buffer: required with image_query=, refused without."""
+        if self.inet is None:
+            if images is not None:
+                raise ValueError("images= needs a trainer built with image_query= (an imagequery.ImageQueryNet)")
+            return
+        if images is None:
+            raise ValueError("image_query: step() needs images= (B, K, h, w), one picture per source")
+        if tuple(images.shape) != tuple(self.images.shape):
+            raise ValueError(f"images {tuple(images.shape)}, expected {tuple(self.images.shape)}")
+        self.images.copy_(images)
+
+    def step(self, raw, gains, spk_idx, lengths=None, images=None):
         """One full training step on device-resident inputs; returns the loss tensor (not synced).  lengths (B, K)
-        int32: each source's own length in samples (zero beyond: ops.mix_sources)."""
+        int32: each source's own length in samples (zero beyond: ops.mix_sources).  images (B, K, h, w): the
+        pictures that name the sources (image_query= only)."""
+        self.set_images(images)
         self.spk.copy_(spk_idx)
         self.features(raw, gains, lengths)
         self.forward()
@@ -882,6 +917,8 @@ class SepTrainer:
 
         if self.vnet is not None:
             raise NotImplementedError("capture(): the voiceprint step is not built for HIP-graph capture; use step()")
+        if self.inet is not None:
+            raise NotImplementedError("capture(): the image-query step is not built for HIP-graph capture; use step()")
         torch.cuda.synchronize()
         g = torch.cuda.CUDAGraph()
         g2 = torch.cuda.CUDAGraph() if self.buckets else None
@@ -923,6 +960,9 @@ class SepTrainer:
         if self.vnet is not None:
             raise NotImplementedError("step_graph(): the voiceprint step is not built for HIP-graph capture; "
                                       "use step()")
+        if self.inet is not None:
+            raise NotImplementedError("step_graph(): the image-query step is not built for HIP-graph capture; "
+                                      "use step()")
         if getattr(self, "graph", None) is None:
             self.capture()
         self.spk.copy_(spk_idx)
@@ -952,7 +992,12 @@ class SepTrainer:
         clip_norm / adv_clip_norm: updates refused only because their gradient held an Inf or NaN are
         taken out of step_count (adv_step_count) in the same way and added to skipped_nonfinite
         (adv_skipped_nonfinite); the device counters are reset and check() returns without raising.  As with
-        time-outs, the bias corrections of the steps enqueued before this check count the skipped step."""
+        time-outs, the bias corrections of the steps enqueued before this check count the skipped step.
+
+        image_query: bit 1 of status[0] is the step's loss guard (dl4ss_imgq_guard: a loss that is not finite).
+        The steps it refused -- the one with that loss and every one enqueued behind it -- are taken out of the
+        step counts in the same way, the status word is reset and check() raises RuntimeError("non-finite loss
+        ...") when bit 1 alone is set; with bit 0 set as well, the time-out's message."""
         torch.cuda.synchronize()
         s, refused = (int(x) for x in self.status.tolist())
         if s or refused:
@@ -964,8 +1009,10 @@ class SepTrainer:
                 opt.settle(timed_out, n)
             if not (s or timed_out):
                 return
+            if s == 2:  # (bit 1: the image-query step's loss guard, dl4ss_imgq_guard)
+                raise RuntimeError(f"non-finite loss: {timed_out} update(s) refused")
             self.rnn_ws_all.zero_()  # a timed-out launch's half-written hand-offs must not reach the next
             if self.vp is not None:
-                self.vp.enc.rnn_ws.zero_()
+                self.vp.reset_workspaces()
             where = "on this rank" if s else "on a data-parallel peer"
             raise RuntimeError(f"BiRNN hand-off timed out {where} (status {s}): {timed_out} update(s) refused")

@@ -25,6 +25,7 @@ import math
 import torch
 
 from . import _lib, ops
+from .imagequery import ImageQueryEncoder, ImageQueryNet
 from .ops import A_SPLIT, CELLS, W_SPLIT, hilo, pad8
 from .params import FlatParams, _ngate
 
@@ -315,7 +316,8 @@ class RecursiveExtractor:
 
 class EnrolledExtractor:
     """Separation of speakers enrolled from clean speech (DL4SS_Keras/predict.py:160-180, 231-233): ``enrol``
-    turns clean excerpts into unit voiceprints with a ``voiceprint.VoiceprintNet``, ``run`` extracts one mask per
+    turns clean excerpts into unit voiceprints with a ``voiceprint.VoiceprintNet`` -- or, given an
+    ``imagequery.ImageQueryNet`` in its place, images (n, h, w) into unit vectors --, ``run`` extracts one mask per
     query from B mixtures of T frames with the mask net (``MaskNetForward`` and one attention launch per query
     over the same V: 'dot' or 'align', as the net is built).  ``precision``: the mask net's, as MaskNetForward;
     the voiceprint encoder is fp32."""
@@ -325,7 +327,12 @@ class EnrolledExtractor:
             raise ValueError("EnrolledExtractor: the magnitude-mask nets only (no cRM)")
         if net.adjust:
             raise ValueError("EnrolledExtractor: net.adjust (ADDJUST works on embedding rows, not on voiceprints)")
-        if net.E != vnet.E or net.F != vnet.F:
+        self.by_image = isinstance(vnet, ImageQueryNet)  # the target is enrolled from a picture, not clean speech
+        if self.by_image:
+            if net.E != vnet.E:
+                raise ValueError(f"EnrolledExtractor: the image encoder gives vectors of {vnet.E}, the net takes "
+                                 f"queries of {net.E}")
+        elif net.E != vnet.E or net.F != vnet.F:
             raise ValueError(f"EnrolledExtractor: the encoder gives ({vnet.F} bins -> {vnet.E}), the net takes "
                              f"({net.F} bins, queries of {net.E})")
         self.net, self.vnet, self.B, self.T, self.K = net, vnet, B, T, K
@@ -341,6 +348,15 @@ class EnrolledExtractor:
         memory row would return for the speaker."""
         from .voiceprint import VoiceprintEncoder, unit
 
+        if self.by_image:  # feats: images (n, h, w); the other arguments belong to the frame mask
+            if rule != "nonzero" or thr is not None or lengths is not None:
+                raise ValueError("EnrolledExtractor.enrol: rule / thr / lengths select frames of clean speech; an "
+                                 "image encoder takes images (n, h, w) alone")
+            n = feats.shape[0]
+            enc = self._enc.get((n,))
+            if enc is None:
+                enc = self._enc[(n,)] = ImageQueryEncoder(self.vnet, n)
+            return unit(enc.forward(feats.contiguous()))
         n, Te, _ = feats.shape
         enc = self._enc.get((n, Te))
         if enc is None:

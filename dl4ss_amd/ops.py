@@ -730,3 +730,73 @@ def spk_memory_store(q, ids, mem, status=None):
     _lib.call("dl4ss_spk_memory_store", _lib.ptr(q), _lib.ptr(ids), n, E, M, _lib.ptr(mem), _lib.ptr(status),
               _lib.stream_ptr())
     return mem
+
+
+# ---- image query (csrc/imgq.hip, include/dl4ss_imgq.h) ----
+def imgq_param_count(h, w, E):
+    """Floats in the image-query encoder's parameter block for (h, w) images and E outputs."""
+    P = _lib.query("dl4ss_imgq_param_count", h=int(h), w=int(w), E=int(E))
+    if P < 0:
+        c = _lib.IMGQ_CONSTANTS
+        raise ValueError(f"image query: images of {h} x {w} with E = {E}: {c['DL4SS_IMGQ_MIN_HW']} <= h, w <= "
+                         f"{c['DL4SS_IMGQ_MAX_HW']} and 1 <= E <= {c['DL4SS_IMGQ_MAX_E']}")
+    return P
+
+
+def _imgq_args(images, params, E, name):
+    _f32c(images, name)
+    _f32c(params, f"{name}(params)")
+    if images.dim() != 3:
+        raise RuntimeError(f"{name}: images (n, h, w)")
+    n, h, w = images.shape
+    P = imgq_param_count(h, w, E)
+    if params.numel() < P:
+        raise RuntimeError(f"{name}: params holds {params.numel()} floats, the encoder has {P}")
+    if n > _lib.IMGQ_CONSTANTS["DL4SS_IMGQ_MAX_N"]:
+        raise RuntimeError(f"{name}: n <= {_lib.IMGQ_CONSTANTS['DL4SS_IMGQ_MAX_N']}")
+    return n, h, w, P
+
+
+def imgq_fwd(images, params, E, vec=None):
+    """images (n, h, w), params (the flat parameter block) -> vec (n, E), every element written."""
+    n, h, w, _ = _imgq_args(images, params, E, "imgq_fwd")
+    vec = torch.empty(n, E, device=images.device, dtype=torch.float32) if vec is None else _f32c(vec, "imgq_fwd(vec)")
+    if vec.numel() != n * E:
+        raise RuntimeError("imgq_fwd: vec must be (n, E)")
+    _lib.call("dl4ss_imgq_fwd", images=_lib.ptr(images), params=_lib.ptr(params), n=n, h=h, w=w, E=int(E),
+              vec=_lib.ptr(vec), stream=_lib.stream_ptr())
+    return vec
+
+
+def imgq_bwd(images, dvec, params, dpart):
+    """dvec (n, E) -> dpart (n, ld): each image's own parameter gradient, columns behind the parameter count zero,
+    every element written (the forward is recomputed from the images)."""
+    _f32c(dvec, "imgq_bwd(dvec)")
+    _f32c(dpart, "imgq_bwd(dpart)")
+    if dvec.dim() != 2 or dpart.dim() != 2:
+        raise RuntimeError("imgq_bwd: dvec (n, E), dpart (n, ld)")
+    E = dvec.shape[1]
+    n, h, w, P = _imgq_args(images, params, E, "imgq_bwd")
+    if dvec.shape[0] != n or dpart.shape[0] != n or dpart.shape[1] < P:
+        raise RuntimeError(f"imgq_bwd: dvec ({n}, E) and dpart ({n}, ld >= {P})")
+    _lib.call("dl4ss_imgq_bwd", images=_lib.ptr(images), dvec=_lib.ptr(dvec), params=_lib.ptr(params), n=n, h=h, w=w,
+              E=E, dpart=_lib.ptr(dpart), ld=dpart.shape[1], dpart_floats=dpart.numel(), stream=_lib.stream_ptr())
+    return dpart
+
+
+def imgq_reduce(dpart, out):
+    """out (ld) = column sums of dpart (n, ld), rows added pairwise in a fixed order (include/dl4ss_imgq.h): the same
+    bits for the same n; every element of out written."""
+    _f32c(dpart, "imgq_reduce")
+    _f32c(out, "imgq_reduce(out)")
+    if dpart.dim() != 2 or out.numel() != dpart.shape[1]:
+        raise RuntimeError("imgq_reduce: dpart (n, ld), out (ld)")
+    _lib.call("dl4ss_imgq_reduce", dpart=_lib.ptr(dpart), n=dpart.shape[0], ld=dpart.shape[1], out=_lib.ptr(out),
+              stream=_lib.stream_ptr())
+    return out
+
+
+def imgq_guard(loss, status):
+    """status[0] |= 2 on device when loss[0] is not finite (the image-query step's refusal of such a step)."""
+    _f32c(loss, "imgq_guard(loss)")
+    _lib.call("dl4ss_imgq_guard", loss=_lib.ptr(loss), status=_lib.ptr(status), stream=_lib.stream_ptr())

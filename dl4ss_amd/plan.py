@@ -5,6 +5,7 @@ import types
 import torch
 
 from . import _lib, ops
+from .imagequery import ImageQueryNet
 from .params import DiscNet, _ngate
 from .voiceprint import SpeakerMemory, VoiceprintNet
 
@@ -14,7 +15,7 @@ def _same_device(net, other):
 
 
 def check_args(net, batch, k, n_samples, mode, precision, rnn_precision, loss_channels, process_group, adversary,
-               clip_norm, adv_clip_norm, vnet, memory, memory_refresh, splitk_reduce="atomic"):
+               clip_norm, adv_clip_norm, vnet, memory, memory_refresh, splitk_reduce="atomic", inet=None):
     """Every combination of SepTrainer's arguments it is not built for, each refused with its reason: host checks
     only, run in front of the first device call.  Returns the clip thresholds as floats (or None)."""
     if mode not in ("label", "pit", "crm"):
@@ -24,7 +25,47 @@ def check_args(net, batch, k, n_samples, mode, precision, rnn_precision, loss_ch
     if splitk_reduce == "fixed" and precision != "fp32":
         raise ValueError(f"splitk_reduce='fixed' is the fp32 step's fixed-order split-K (precision {precision!r}: "
                          "the bf16 steps' split-K is already deterministic)")
-    if vnet is not None or memory is not None:  # everything the voiceprint step is not built for
+    if inet is not None:  # everything the image-query step is not built for (the voiceprint step's list)
+        if vnet is not None:
+            raise ValueError("image_query: given together with voiceprint=, a step has one query encoder")
+        if memory is None:
+            raise ValueError("image_query: the encoder needs memory= (a voiceprint.SpeakerMemory)")
+        if not isinstance(inet, ImageQueryNet):
+            raise ValueError("image_query: expected an imagequery.ImageQueryNet")
+        if not isinstance(memory, SpeakerMemory):
+            raise ValueError("memory: expected a voiceprint.SpeakerMemory")
+        if mode != "label":
+            raise ValueError(f"image_query: mode {mode!r} is unsupported, the query by image belongs to its own "
+                             "source (mode 'label')")
+        if net.crm:
+            raise ValueError("image_query: a cRM net (query width 2E) is unsupported")
+        if net.adjust:
+            raise ValueError("image_query: net.adjust is unsupported (ADDJUST adds to an embedding row, not to a "
+                             "memory row); build the SepNet with adjust=False")
+        if net.E != inet.E:
+            raise ValueError(f"image_query: the encoder's vectors have {inet.E} elements, the net's queries {net.E}")
+        if memory.E != inet.E:
+            raise ValueError(f"memory: rows of {memory.E} elements, the encoder's vectors have {inet.E}")
+        if precision != "fp32":
+            raise ValueError(f"image_query: precision {precision!r} is unsupported, the image-query path is fp32")
+        if loss_channels:
+            raise ValueError("image_query: loss_channels is unsupported")
+        if adversary is not None:
+            raise ValueError("image_query: an adversary is unsupported")
+        if process_group is not None:
+            raise ValueError("image_query: no data-parallel image-query step (process_group; the encoder's "
+                             "gradient and the memory are not all-reduced)")
+        if clip_norm is not None:
+            raise ValueError("image_query: clip_norm is unsupported (one global norm over the two flat gradients "
+                             "needs a kernel change)")
+        if memory_refresh not in ("reference", "reuse"):
+            raise ValueError(f"memory_refresh {memory_refresh!r}: expected 'reference' or 'reuse'")
+        if batch * k > 1024:
+            raise ValueError(f"image_query: {batch * k} sources per step, the memory kernels take at most 1024")
+        for what, other in (("image_query", inet), ("memory", memory)):
+            if not _same_device(net, other):
+                raise ValueError(f"{what}: lives on another device than the net")
+    elif vnet is not None or memory is not None:  # everything the voiceprint step is not built for
         if vnet is None:
             raise ValueError("memory: a SpeakerMemory needs voiceprint= (the encoder whose vectors it accumulates)")
         if memory is None:

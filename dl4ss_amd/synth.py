@@ -78,3 +78,46 @@ def gains_for(u, k, db=5.0):
         g[:, 1] = 10.0 ** (db / 20.0 * (0.5 + 0.5 * u[:, 0]))
         g[:, 2] = 10.0 ** (db / 20.0 * (0.5 * u[:, 1]))
     return g
+
+
+class Glyphs:
+    """``templates`` (num_classes, h, w) float32 in [0, 1]: per class a few seeded strokes on an exactly-zero
+    background -- the stand-in for MNIST digits (flat background, a class-specific shape).  ``draw(labels, rng)``:
+    one jittered image per label -- the template moved by up to 2 pixels each way (zero fill) and scaled by
+    U[0.7, 1]; the background stays exactly zero."""
+
+    def __init__(self, num_classes, size=(28, 28), seed=1):
+        h, w = size
+        rng = np.random.Generator(np.random.PCG64(seed))
+        yy, xx = np.mgrid[0:h, 0:w].astype(np.float64)
+        self.templates = np.zeros((num_classes, h, w), dtype=np.float32)
+        for c in range(num_classes):
+            img = np.zeros((h, w))
+            p = rng.uniform(0.2, 0.8, size=2) * (h - 1, w - 1)
+            for _ in range(3):  # a polyline of three strokes inside the central region
+                q = rng.uniform(0.15, 0.85, size=2) * (h - 1, w - 1)
+                d = q - p
+                t = np.clip(((yy - p[0]) * d[0] + (xx - p[1]) * d[1]) / max(d @ d, 1e-9), 0.0, 1.0)
+                dist = np.hypot(yy - (p[0] + t * d[0]), xx - (p[1] + t * d[1]))
+                img = np.maximum(img, np.clip(1.6 - dist, 0.0, 1.0))  # exactly zero beyond 1.6 pixels
+                p = q
+            self.templates[c] = img
+        self.num_classes, self.size = num_classes, (h, w)
+
+    def draw(self, labels, rng):
+        labels = np.asarray(labels).reshape(-1)
+        h, w = self.size
+        out = np.zeros((labels.size, h, w), dtype=np.float32)
+        for i, c in enumerate(labels):
+            dy, dx = (int(v) for v in rng.integers(-2, 3, size=2))
+            src = self.templates[int(c)]
+            ys, yd = (slice(0, h - dy), slice(dy, h)) if dy >= 0 else (slice(-dy, h), slice(0, h + dy))
+            xs, xd = (slice(0, w - dx), slice(dx, w)) if dx >= 0 else (slice(-dx, w), slice(0, w + dx))
+            out[i][yd, xd] = src[ys, xs] * np.float32(rng.uniform(0.7, 1.0))
+        return out
+
+
+def glyphs(num_classes, size=(28, 28), seed=1):
+    """Deterministic stroke images, one template per class (Glyphs): what the image-query tests and bench use
+    where the reference reads MNIST."""
+    return Glyphs(num_classes, size, seed)

@@ -198,31 +198,32 @@ class VoiceprintEncoder:
             raise RuntimeError(f"BiRNN hand-off timed out (status {s})")
 
 
-class VoiceprintStep:
-    """The voiceprint queries of a training step (SepTrainer(voiceprint=, memory=)): the encoder over the step's clean
-    magnitudes ``mag_src`` (B, K, T, F), the memory, the encoder's guarded Adam and the memory refresh.  ``spk``,
-    ``q``, ``dq``, ``status``, ``loss``: the trainer's buffers (the trainer itself is not referenced: _ws_slot)."""
+class MemoryQueryStep:
+    """What the query steps of a trainer share (the voiceprint step below, imagequery.ImageQueryStep): the speaker
+    memory forward / backward around an encoder, the encoder's guarded Adam and the memory refresh.  A subclass
+    builds ``enc`` (``forward(x) -> vec (n, E)``, ``backward(dvec) -> net.grad``, ``vec`` the forward's output)
+    and says what it reads (``encoder_input``).  ``spk``, ``q``, ``dq``, ``status``, ``loss``: the trainer's
+    buffers (the trainer itself is not referenced: _ws_slot)."""
 
-    def __init__(self, vnet, memory, refresh, mag_src, spk, q, dq, status, loss, lr, betas, eps, wgrad_split=1):
-        B, K, T, F = mag_src.shape
-        f32 = dict(device=vnet.device, dtype=torch.float32)
-        self.net, self.memory, self.refresh = vnet, memory, refresh
-        self.maps, self.spk, self.q, self.dq = mag_src.view(B * K, T, F), spk.view(-1), q, dq.view(B * K, -1)
-        # its recurrences share the step's status word
-        self.enc = VoiceprintEncoder(vnet, B * K, T, status=status, wgrad_split=wgrad_split)
-        self.u, self.dv, self.q2 = (torch.empty(B * K, vnet.E, **f32) for _ in range(3))  # q2: the refreshed rows
-        self.opt = GuardedAdam(vnet.flat, status, loss, lr, betas, eps)
+    def __init__(self, net, memory, refresh, enc, spk, q, dq, status, loss, lr, betas, eps):
+        n = spk.numel()
+        f32 = dict(device=net.device, dtype=torch.float32)
+        self.net, self.memory, self.refresh, self.enc, self.status = net, memory, refresh, enc, status
+        self.spk, self.q, self.dq = spk.view(-1), q, dq.view(n, -1)
+        self.u, self.dv, self.q2 = (torch.empty(n, net.E, **f32) for _ in range(3))  # q2: the refreshed rows
+        self.opt = GuardedAdam(net.flat, status, loss, lr, betas, eps)
+
+    def encoder_input(self):
+        raise NotImplementedError
 
     def queries(self, q):
-        """q (B, K, E) = the memory rows of the step's speakers with this batch's unit voiceprints accumulated:
-        the masked encoder over the clean magnitudes the step's STFT wrote (silent frames, e.g. the zero tail of
-        a short source, are masked: rule 'nonzero'), then the memory forward.  (The STFT transforms frames in
-        pairs: a silent frame that shares its transform with a voiced one -- the first silent frame behind an odd
-        number of voiced ones -- carries that neighbour's rounding residue, ~1e-8 of it, and counts as valid.)"""
-        ops.spk_memory_fwd(self.enc.forward(self.maps), self.spk, self.memory.mem, u=self.u, q=q.view(self.u.shape))
+        """q (B, K, E) = the memory rows of the step's speakers with this batch's unit vectors accumulated: the
+        encoder over its input, then the memory forward."""
+        ops.spk_memory_fwd(self.enc.forward(self.encoder_input()), self.spk, self.memory.mem, u=self.u,
+                           q=q.view(self.u.shape))
 
     def backward(self):
-        """dq -> the voiceprints' gradient through the memory, then the encoder's BPTT into net.grad (all written)."""
+        """dq -> the vectors' gradient through the memory, then the encoder's backward into net.grad (all written)."""
         ops.spk_memory_bwd(self.dq, self.enc.vec, self.u, self.spk, self.memory.mem, dv=self.dv)
         self.enc.backward(self.dv)
 
@@ -234,7 +235,33 @@ class VoiceprintStep:
         if self.refresh == "reference":
             q = self.q2
             self.queries(q)
-        ops.spk_memory_store(q.view(self.u.shape), self.spk, self.memory.mem, status=self.enc.status)
+        ops.spk_memory_store(q.view(self.u.shape), self.spk, self.memory.mem, status=self.status)
+
+    def reset_workspaces(self):
+        """After a timed-out hand-off: nothing to reset unless the encoder has recurrences."""
+
+
+class VoiceprintStep(MemoryQueryStep):
+    """The voiceprint queries of a training step (SepTrainer(voiceprint=, memory=)): the encoder over the step's clean
+    magnitudes ``mag_src`` (B, K, T, F), the memory, the encoder's guarded Adam and the memory refresh.
+
+    The masked encoder reads the clean magnitudes the step's STFT wrote (silent frames, e.g. the zero tail of
+    a short source, are masked: rule 'nonzero').  (The STFT transforms frames in
+    pairs: a silent frame that shares its transform with a voiced one -- the first silent frame behind an odd
+    number of voiced ones -- carries that neighbour's rounding residue, ~1e-8 of it, and counts as valid.)"""
+
+    def __init__(self, vnet, memory, refresh, mag_src, spk, q, dq, status, loss, lr, betas, eps, wgrad_split=1):
+        B, K, T, F = mag_src.shape
+        self.maps = mag_src.view(B * K, T, F)
+        # its recurrences share the step's status word
+        enc = VoiceprintEncoder(vnet, B * K, T, status=status, wgrad_split=wgrad_split)
+        super().__init__(vnet, memory, refresh, enc, spk, q, dq, status, loss, lr, betas, eps)
+
+    def encoder_input(self):
+        return self.maps
+
+    def reset_workspaces(self):
+        self.enc.rnn_ws.zero_()
 
 
 def unit(vec):
