@@ -1,5 +1,6 @@
 """ctypes binding of ``libdl4ss_hip.so``, derived from the C ABI's one declaration, ``include/dl4ss_hip.h``
-(and ``include/dl4ss_imgq.h``, the image-query encoder's entry points, parsed the same way into ``IMGQ_*`` tables).
+(and ``include/dl4ss_imgq.h``, the image-query encoder's entry points, and ``include/dl4ss_optim.h``, Nadam and
+Keras's clipnorm, parsed the same way into ``IMGQ_*`` and ``OPTIM_*`` tables).
 
 The header is parsed once at import: every prototype gives the entry point's ``argtypes`` (``SIGNATURES``), its
 ``restype`` (``RESTYPES``) and its parameter names (``PARAMS``); every enum constant and ``#define DL4SS_* <integer>``
@@ -26,14 +27,16 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("DL4SS_LIB", os.path.join(_HERE, "libdl4ss_hip.so"))
 HEADER = os.path.join(os.path.dirname(_HERE), "include", "dl4ss_hip.h")
 IMGQ_HEADER = os.path.join(os.path.dirname(_HERE), "include", "dl4ss_imgq.h")  # the image-query encoder's entry points
+OPTIM_HEADER = os.path.join(os.path.dirname(_HERE), "include", "dl4ss_optim.h")  # Nadam, Keras's clipnorm
 
 P = ctypes.c_void_p
 I = ctypes.c_int
 LL = ctypes.c_longlong
 F = ctypes.c_float
 U = ctypes.c_uint
+D = ctypes.c_double
 
-_VALUE = {"int": I, "long long": LL, "float": F, "unsigned": U}  # by-value parameter types
+_VALUE = {"int": I, "long long": LL, "float": F, "unsigned": U, "double": D}  # by-value parameter types
 _POINTEE = set(_VALUE) | {"void", "double"}  # what a pointer or array parameter may point at
 _RETURN = {"int": I, "long long": LL, "void": None}
 _PROTO = re.compile(r"(int|long long|void)\s+(dl4ss_\w+)\s*\(([^()]*)\)\s*;")
@@ -87,10 +90,16 @@ with open(IMGQ_HEADER) as _f:
     IMGQ_SIGNATURES, IMGQ_RESTYPES, IMGQ_PARAMS, IMGQ_CONSTANTS = parse_header(_f.read(), "dl4ss_imgq.h")
 if set(IMGQ_SIGNATURES) & set(SIGNATURES):
     raise ValueError(f"dl4ss_imgq.h declares again: {sorted(set(IMGQ_SIGNATURES) & set(SIGNATURES))}")
+# the third, likewise
+with open(OPTIM_HEADER) as _f:
+    OPTIM_SIGNATURES, OPTIM_RESTYPES, OPTIM_PARAMS, OPTIM_CONSTANTS = parse_header(_f.read(), "dl4ss_optim.h")
+if set(OPTIM_SIGNATURES) & (set(SIGNATURES) | set(IMGQ_SIGNATURES)):
+    raise ValueError("dl4ss_optim.h declares again: "
+                     f"{sorted(set(OPTIM_SIGNATURES) & (set(SIGNATURES) | set(IMGQ_SIGNATURES)))}")
+_ALL_PARAMS = {**PARAMS, **IMGQ_PARAMS, **OPTIM_PARAMS}
 # keyword -> slot of every entry point (a header name that is a Python keyword takes a trailing underscore)
 _SLOTS = {name: {p + "_" if keyword.iskeyword(p) else p: i for i, p in enumerate(ps)}
-          for name, ps in {**PARAMS, **IMGQ_PARAMS}.items()}
-_ALL_PARAMS = {**PARAMS, **IMGQ_PARAMS}
+          for name, ps in _ALL_PARAMS.items()}
 # knobs the library itself used to read from the environment, retired with plan.RETIRED_KNOBS
 RETIRED_ENV = ("DL4SS_ATTN_TILES", "DL4SS_RNN_MAX_WG", "DL4SS_RNN_MIN_BC")
 
@@ -113,14 +122,16 @@ def _load():
         fn = getattr(lib, name)
         fn.argtypes = argtypes
         fn.restype = RESTYPES[name]
-    # the second header's entry points.  A library without them still loads: the binding tests stand a stub with
-    # the first header's names alone in for the library, and DL4SS_LIB may name a build from before imgq.hip.
-    # Calling one that is missing fails in ctypes' own lookup, with the symbol's name: there is no other path
-    for name, argtypes in IMGQ_SIGNATURES.items():
-        fn = getattr(lib, name, None)
-        if fn is not None:
-            fn.argtypes = argtypes
-            fn.restype = IMGQ_RESTYPES[name]
+    # the second and third headers' entry points.  A library without them still loads: the binding tests stand a
+    # stub with the first header's names alone in for the library, and DL4SS_LIB may name a build from before
+    # imgq.hip or optim.hip.  Calling one that is missing fails in ctypes' own lookup, with the symbol's name:
+    # there is no other path
+    for sigs, restypes in ((IMGQ_SIGNATURES, IMGQ_RESTYPES), (OPTIM_SIGNATURES, OPTIM_RESTYPES)):
+        for name, argtypes in sigs.items():
+            fn = getattr(lib, name, None)
+            if fn is not None:
+                fn.argtypes = argtypes
+                fn.restype = restypes[name]
     hip = ctypes.CDLL("libamdhip64.so")
     hip.hipGetErrorString.restype = ctypes.c_char_p
     hip.hipGetErrorString.argtypes = [ctypes.c_int]
@@ -139,6 +150,10 @@ def exported_symbols():
 
 def imgq_exported_symbols():
     return list(IMGQ_SIGNATURES)
+
+
+def optim_exported_symbols():
+    return list(OPTIM_SIGNATURES)
 
 
 def stream_ptr(stream=None):
@@ -164,7 +179,8 @@ def bind(name, args, kw):
     ``TypeError`` unless every parameter of the prototype is given exactly once."""
     slots = _SLOTS.get(name)
     if slots is None:
-        raise TypeError(f"{name} is not declared in include/dl4ss_hip.h or include/dl4ss_imgq.h")
+        raise TypeError(f"{name} is not declared in include/dl4ss_hip.h, include/dl4ss_imgq.h or "
+                        "include/dl4ss_optim.h")
     n, given = len(slots), len(args) + len(kw)
     if len(args) > n:
         raise TypeError(f"{name} takes {n} arguments (the last is {_ALL_PARAMS[name][-1]!r}), {given} given")

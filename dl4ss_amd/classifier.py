@@ -15,7 +15,7 @@ guarded Adam (``optimizer_step``).  Single GPU, eager launches (no HIP-graph cap
 """
 import torch
 
-from . import _lib, adam, ops
+from . import _lib, adam, ops, plan
 
 LSTM = 0
 
@@ -28,12 +28,17 @@ class ClassifierTrainer:
     ``clip_norm``: clip the gradient's global L2 norm to it on device (torch.nn.utils.clip_grad_norm_'s
     arithmetic; +inf: measure and guard only), and refuse an update whose gradient holds an Inf or NaN;
     ``grad_norm`` (device float[2], valid after optimizer_step(), not synced) then holds the norm before
-    clipping and the coefficient.  None: no extra launch, the unclipped step."""
+    clipping and the coefficient.  None: no extra launch, the unclipped step.
+    ``optimizer`` "nadam": Keras 1's Nadam with ``schedule_decay`` instead of Adam; ``clipnorm``: the clip by
+    Keras's rule (c = clipnorm / norm where norm >= clipnorm, else 1), otherwise as ``clip_norm``; the two
+    together are refused (SepTrainer has the same three arguments)."""
 
     def __init__(self, cnet, batch, k, n_samples, precision="fp32", lr=1e-5, betas=(0.9, 0.999), eps=1e-8,
-                 clip_norm=None):
+                 clip_norm=None, optimizer="adam", schedule_decay=0.004, clipnorm=None):
         if precision not in ops.PREC:
             raise ValueError(f"precision {precision!r}: expected one of {sorted(ops.PREC)}")
+        self.clipnorm = plan.check_optimizer(optimizer, schedule_decay, clip_norm, clipnorm)
+        self.optimizer, self.schedule_decay = optimizer, float(schedule_decay)
         self.clip_norm = None if clip_norm is None else ops.check_clip_norm(clip_norm)
         self.net, self.B, self.K, self.N = cnet, batch, k, n_samples
         self.precision = precision
@@ -70,9 +75,10 @@ class ClassifierTrainer:
         self.rnn_ws = torch.zeros((ws + 7) // 8, device=dev, dtype=torch.int64)
         self.status = torch.zeros(2, device=dev, dtype=torch.int32)  # {hand-off timed out, refused updates}
         cnet.grad = torch.zeros_like(cnet.flat)
-        self.opt = adam.GuardedAdam(cnet.flat, self.status, self.loss, lr, betas, eps, clip_norm=self.clip_norm)
+        self.opt = adam.GuardedAdam(cnet.flat, self.status, self.loss, lr, betas, eps, clip_norm=self.clip_norm,
+                                    kind=optimizer, schedule_decay=schedule_decay, clipnorm=self.clipnorm)
         self.m, self.v = self.opt.m, self.opt.v
-        if self.clip_norm is not None:
+        if self.opt.clip is not None:
             self.grad_norm = self.opt.grad_norm
 
     # the documented scalars live in the optimizer, read / write (schedule.classifier() assigns lr)

@@ -2,6 +2,7 @@
 // ADDJUST), their backward, bias column sums, the gradient's sum of squares (global-norm clip) and the Adam
 // update.
 #include "common.h"
+#include "update.h"
 
 namespace {
 
@@ -297,49 +298,7 @@ __global__ __launch_bounds__(256) void colsum_kernel(const float* __restrict__ A
   if (rl == 0 && c < N) atomicAdd(out + c, s[0][threadIdx.x] + s[1][threadIdx.x] + s[2][threadIdx.x] + s[3][threadIdx.x]);
 }
 
-// bf16 shadow copies written by the Adam update (the bf16 step's GEMM / recurrence operands): segment s
-// maps the flat range [off, off + rows*cols) row-major onto y[r * ldy + c] (columns >= cols untouched)
-constexpr int SHADOW_MAX = 8;
-struct ShadowSegs {
-  long long off[SHADOW_MAX], len[SHADOW_MAX], ldy[SHADOW_MAX];
-  int cols[SHADOW_MAX];
-  unsigned short* y[SHADOW_MAX];
-  int n;
-};
-__device__ __forceinline__ void shadow_store(const ShadowSegs& sh, long long i, float x) {
-#pragma unroll
-  for (int s = 0; s < SHADOW_MAX; ++s) {
-    if (s >= sh.n) break;
-    const long long j = i - sh.off[s];
-    if (j >= 0 && j < sh.len[s]) {
-      const unsigned r = (unsigned)j / (unsigned)sh.cols[s], c = (unsigned)j - r * (unsigned)sh.cols[s];
-      sh.y[s][r * sh.ldy[s] + c] = (unsigned short)bf16_bits_rne(x);
-      return;
-    }
-  }
-}
-// four consecutive flat elements i..i+3: one 8-B store when they sit in one row of one segment at
-// an 8-B aligned destination (the 600-column weights: every quad), else element by element
-__device__ __forceinline__ void shadow_store4(const ShadowSegs& sh, long long i, float4 x) {
-#pragma unroll
-  for (int s = 0; s < SHADOW_MAX; ++s) {
-    if (s >= sh.n) break;
-    const long long j = i - sh.off[s];
-    if (j + 3 < 0 || j >= sh.len[s]) continue;
-    if (j >= 0 && j + 3 < sh.len[s]) {
-      const unsigned r = (unsigned)j / (unsigned)sh.cols[s], c = (unsigned)j - r * (unsigned)sh.cols[s];
-      const long long o = r * sh.ldy[s] + c;
-      if (c + 3 < (unsigned)sh.cols[s] && (o & 3) == 0) {
-        const unsigned lo = bf16_bits_rne(x.x) | (bf16_bits_rne(x.y) << 16);
-        const unsigned hi = bf16_bits_rne(x.z) | (bf16_bits_rne(x.w) << 16);
-        *reinterpret_cast<uint2*>(sh.y[s] + o) = make_uint2(lo, hi);
-        return;
-      }
-    }
-    break;  // a quad across a row or segment boundary
-  }
-  shadow_store(sh, i, x.x); shadow_store(sh, i + 1, x.y); shadow_store(sh, i + 2, x.z); shadow_store(sh, i + 3, x.w);
-}
+// (the bf16 shadow stores, block_sum_d and the update kernel itself: update.h, shared with optim.hip)
 
 // Sum of squares of the flat gradient for the global-norm clip: part[j] = the fp64 sum of g[i]^2 over the
 // j-th contiguous range of `per` quads (the n % 4 tail goes to the last range).  The ranges and the order of
@@ -356,14 +315,6 @@ static inline long long sumsq_parts(long long n) {
 __device__ __forceinline__ double sq4(float4 x, double acc) {
   const double a = (double)x.x, b = (double)x.y, c = (double)x.z, d = (double)x.w;
   return fma(d, d, fma(c, c, fma(b, b, fma(a, a, acc))));
-}
-// every thread of a 256-thread block gets the sum of the block's values (a fixed tree: butterfly inside
-// each wave, then the four wave sums in wave order)
-__device__ __forceinline__ double block_sum_d(double v, double* sd) {
-  v = wave_sum_d(v);
-  if ((threadIdx.x & 63) == 0) sd[threadIdx.x >> 6] = v;
-  __syncthreads();
-  return ((sd[0] + sd[1]) + sd[2]) + sd[3];
 }
 __global__ __launch_bounds__(SUMSQ_THREADS) void grad_sumsq_kernel(const float* __restrict__ g, long long n,
                                                                    long long per, double* __restrict__ part) {
@@ -383,90 +334,6 @@ __global__ __launch_bounds__(SUMSQ_THREADS) void grad_sumsq_kernel(const float* 
     for (long long i = nq << 2; i < n; ++i) a1 = fma((double)g[i], (double)g[i], a1);
   const double s = block_sum_d(a0 + a1, sd);
   if (threadIdx.x == 0) part[blockIdx.x] = s;
-}
-
-// the clipped update's extra arguments (adam_kernel<SH, true>)
-struct ClipArgs {
-  const double* part;  // grad_sumsq_kernel's partials
-  int n_part;
-  float max_norm;
-  float* gnorm;        // [2]: the norm of the mean gradient before clipping, the coefficient c (may be NULL)
-  int* nonfinite;      // [1]: updates refused for a non-finite gradient
-};
-
-// torch.optim.Adam (weight_decay 0, amsgrad off; m via lerp as torch) on flat fp32 buffers
-// (EvalVer.py:538-544,673-675: Adam(lr=2e-4), betas (0.9, 0.999), eps 1e-8).  SH: also the bf16
-// shadow copies of the updated parameters (bitwise dl4ss_f32_to_bf16_2d_multi of the new values).
-// CLIP: the global-norm clip of torch.nn.utils.clip_grad_norm_ on the mean gradient, folded into gscale.
-// Every block sums the partials in the same fixed order (<= 8 KB from L2) and so forms the same factor, or
-// takes the same refusal when the sum is not finite; without CLIP the code is the unclipped kernel's.
-template <bool SH, bool CLIP>
-__global__ __launch_bounds__(256) void adam_kernel(float* __restrict__ p, const float* __restrict__ g,
-                                                   float* __restrict__ m, float* __restrict__ v, long long n,
-                                                   float lr, float b1, float b2, float eps, float bc1, float bc2s,
-                                                   const int* __restrict__ status, int* __restrict__ refused,
-                                                   const float* __restrict__ dp_flag, float gscale,
-                                                   float* __restrict__ loss, ShadowSegs sh, ClipArgs cl) {
-  // refuse the update when a recurrence hand-off of this step timed out on this rank
-  // (status[0]) or on any data-parallel peer (dp_flag: the all-reduced status flag)
-  if ((status && status[0]) || (dp_flag && dp_flag[0] != 0.f)) {
-    if (blockIdx.x == 0 && threadIdx.x == 0) {
-      if (loss) loss[0] = __builtin_nanf("");
-      if (refused) refused[0] += 1;  // refused-update count: the host rolls its step count back by it
-    }
-    return;
-  }
-  if constexpr (CLIP) {
-    __shared__ double sd[4];
-    double s = 0.0;
-    for (int j = threadIdx.x; j < cl.n_part; j += 256) s += cl.part[j];
-    s = block_sum_d(s, sd);
-    // fp64 throughout: nrm = ||g * gscale||, c = min(1, max_norm / (nrm + 1e-6)), one fp32 factor f = gscale c
-    const double nrm = (double)gscale * sqrt(s);
-    const double c = fmin(1.0, (double)cl.max_norm / (nrm + 1e-6));
-    if (!isfinite(s)) {  // an Inf or NaN in the gradient: refused as a timed-out step is, and counted
-      if (blockIdx.x == 0 && threadIdx.x == 0) {
-        if (loss) loss[0] = __builtin_nanf("");
-        if (refused) refused[0] += 1;
-        cl.nonfinite[0] += 1;
-        if (cl.gnorm) { cl.gnorm[0] = (float)nrm; cl.gnorm[1] = 0.f; }
-      }
-      return;
-    }
-    if (blockIdx.x == 0 && threadIdx.x == 0 && cl.gnorm) { cl.gnorm[0] = (float)nrm; cl.gnorm[1] = (float)c; }
-    gscale = (float)((double)gscale * c);  // c == 1: bitwise gscale
-  }
-  const float step = lr / bc1;
-  for (long long i = (blockIdx.x * (long long)blockDim.x + threadIdx.x) * 4; i < n;
-       i += (long long)gridDim.x * blockDim.x * 4) {
-    if (i + 3 < n) {
-      float4 pp = *reinterpret_cast<float4*>(p + i);
-      float4 gg = *reinterpret_cast<const float4*>(g + i);
-      gg.x *= gscale; gg.y *= gscale; gg.z *= gscale; gg.w *= gscale;  // 1 / world (DP SUM); 1: exact
-      float4 mm = *reinterpret_cast<float4*>(m + i);
-      float4 vv = *reinterpret_cast<float4*>(v + i);
-#define ADAM1(c)                                              \
-  mm.c = mm.c + (1.f - b1) * (gg.c - mm.c);                    \
-  vv.c = b2 * vv.c + (1.f - b2) * gg.c * gg.c;                 \
-  pp.c -= step * (mm.c / (sqrtf(vv.c) / bc2s + eps));
-      ADAM1(x) ADAM1(y) ADAM1(z) ADAM1(w)
-#undef ADAM1
-      *reinterpret_cast<float4*>(p + i) = pp;
-      *reinterpret_cast<float4*>(m + i) = mm;
-      *reinterpret_cast<float4*>(v + i) = vv;
-      if constexpr (SH) {
-        shadow_store4(sh, i, pp);
-      }
-    } else {
-      for (long long j = i; j < n; ++j) {
-        const float gj = g[j] * gscale;
-        m[j] = m[j] + (1.f - b1) * (gj - m[j]);
-        v[j] = b2 * v[j] + (1.f - b2) * gj * gj;
-        p[j] -= step * (m[j] / (sqrtf(v[j]) / bc2s + eps));
-        if constexpr (SH) shadow_store(sh, j, p[j]);
-      }
-    }
-  }
 }
 
 }  // namespace
@@ -539,28 +406,13 @@ DL4SS_API int dl4ss_colsum(const float* A, long long lda, int M, int N, float* o
 }
 
 namespace {
+// update.h's kernel as Adam, unclipped or (cl) with torch's clip
 int adam_launch(float* p, const float* g, float* m, float* v, long long n, float lr, float beta1, float beta2,
-                float eps, int step, const int* status, int* refused, const float* dp_flag, float gscale,
+                float eps, int step, int* status, int* refused, const float* dp_flag, float gscale,
                 float* loss, void* stream, const ShadowSegs* sh = nullptr, const ClipArgs* cl = nullptr) {
-  DL4SS_REQUIRE(p && g && m && v && n >= 0 && step >= 1);
-  if (n == 0) return 0;
-  // bias corrections in double on the host, as torch computes them in Python floats
-  const float bc1 = (float)(1.0 - pow((double)beta1, (double)step));
-  const float bc2s = (float)sqrt(1.0 - pow((double)beta2, (double)step));
-  const unsigned grid = (unsigned)min(8192LL, (n / 4 + 255) / 256 + 1);
-  const bool shadows = sh && sh->n > 0;
-#define ADAM_LAUNCH(SH_, CLIP_)                                                                                      \
-  hipLaunchKernelGGL((adam_kernel<SH_, CLIP_>), dim3(grid), dim3(256), 0, as_stream(stream), p, g, m, v, n, lr, beta1, \
-                     beta2, eps, bc1, bc2s, status, refused, dp_flag, gscale, loss, shadows ? *sh : ShadowSegs{},      \
-                     cl ? *cl : ClipArgs{})
-  if (cl) {
-    if (shadows) ADAM_LAUNCH(true, true); else ADAM_LAUNCH(false, true);
-  } else {
-    if (shadows) ADAM_LAUNCH(true, false); else ADAM_LAUNCH(false, false);
-  }
-#undef ADAM_LAUNCH
-  DL4SS_CHECK_LAUNCH();
-  return 0;
+  DL4SS_REQUIRE(step >= 1);
+  return update_launch(adam_scalars(beta1, beta2, step), cl ? CLIP_TORCH : CLIP_NONE, p, g, m, v, n, lr, beta1, beta2,
+                       eps, status, refused, dp_flag, gscale, loss, stream, sh, cl);
 }
 }  // namespace
 
@@ -601,26 +453,6 @@ DL4SS_API int dl4ss_status_flag(const int* status, float* flag, void* stream) {
   DL4SS_CHECK_LAUNCH();
   return 0;
 }
-
-namespace {
-// the shadow-segment arrays of the entry points below, checked and packed for the kernel
-int shadow_segs(ShadowSegs& sh, long long n, int nseg, const long long* seg_off, const int* seg_rows,
-                const int* seg_cols, void* const* seg_y, const long long* seg_ldy) {
-  DL4SS_REQUIRE(nseg >= 0 && nseg <= SHADOW_MAX && (nseg == 0 || (seg_off && seg_rows && seg_cols && seg_y && seg_ldy)));
-  sh.n = nseg;
-  for (int i = 0; i < nseg; ++i) {
-    DL4SS_REQUIRE(seg_y[i] && seg_rows[i] >= 0 && seg_cols[i] > 0 && seg_ldy[i] >= seg_cols[i] && seg_off[i] >= 0 &&
-                  seg_off[i] + (long long)seg_rows[i] * seg_cols[i] <= n && (long long)seg_rows[i] * seg_cols[i] < (1LL << 31));
-    DL4SS_REQUIRE(((uintptr_t)seg_y[i] & 7) == 0);  // the 8-B quad stores
-    sh.off[i] = seg_off[i];
-    sh.len[i] = (long long)seg_rows[i] * seg_cols[i];
-    sh.cols[i] = seg_cols[i];
-    sh.ldy[i] = seg_ldy[i];
-    sh.y[i] = reinterpret_cast<unsigned short*>(seg_y[i]);
-  }
-  return 0;
-}
-}  // namespace
 
 // dl4ss_adam_guarded_dp_scaled that also writes bf16 shadow copies of the updated parameters: segment
 // s (s < nseg <= 8) maps the flat range [seg_off, seg_off + rows*cols) row-major onto seg_y (row stride
@@ -666,7 +498,7 @@ DL4SS_API int dl4ss_adam_clipped(float* p, const float* g, float* m, float* v, l
     return adam_launch(p, g, m, v, n, lr, beta1, beta2, eps, step, status, status ? status + 1 : nullptr, dp_flag,
                        gscale, loss, stream, &sh);
   DL4SS_REQUIRE(n_part == sumsq_parts(n) && max_norm > 0.f && nonfinite && ((uintptr_t)part & 7) == 0);
-  const ClipArgs cl{part, n_part, max_norm, gnorm, nonfinite};
+  const ClipArgs cl{part, n_part, max_norm, gnorm, nonfinite, 0};
   return adam_launch(p, g, m, v, n, lr, beta1, beta2, eps, step, status, status ? status + 1 : nullptr, dp_flag, gscale,
                      loss, stream, &sh, &cl);
 }

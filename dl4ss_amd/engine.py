@@ -37,6 +37,15 @@ class SepTrainer:
     coefficient, ``skipped_nonfinite`` what check() has counted.  ``adv_clip_norm``: the same for each of the
     Discriminator's updates (``adv_grad_norm``, float[2, 2]).  None (the default): no launch is added.
 
+    ``optimizer`` "nadam": the mask net and the query encoder (voiceprint= / image_query=) train with Keras 1's
+    Nadam (DL4SS_Keras/nnet.py:23,113; ``schedule_decay``, default 0.004) instead of Adam -- eager and in
+    step_graph(), fp32 and bf16 (the shadows come from the same launch), data parallel; the Discriminator keeps
+    Adam, as the reference trains it.  ``clipnorm``: the global-norm clip by Keras's rule (c = clipnorm / norm where
+    norm >= clipnorm, else 1), with either optimizer, otherwise as ``clip_norm`` (``grad_norm``,
+    ``skipped_nonfinite``); the two together are refused.  With voiceprint= / image_query= it is the JOINT norm
+    over the net's and the encoder's gradients, as Keras takes it: both ``grad_norm`` and ``vp_opt.grad_norm``
+    hold it, and a joint norm that is not finite refuses both updates and the memory store (check() raises).
+
     ``voiceprint`` (a ``voiceprint.VoiceprintNet``) with ``memory`` (a ``voiceprint.SpeakerMemory``): the queries
     are not rows of ``emb.layer.weight`` but voiceprints -- the masked encoder over the step's own clean
     magnitudes, accumulated into and read back from the speaker memory (DL4SS_Keras/nnet.py:64-92); the encoder
@@ -65,11 +74,14 @@ class SepTrainer:
                  loss_channels=None, betas=(0.9, 0.999), eps=1e-8, process_group=None, rnn_precision=None,
                  adversary=None, adv_weight=1.0, adv_lr=None, disc_adv_update=True, clip_norm=None,
                  adv_clip_norm=None, voiceprint=None, memory=None, voiceprint_lr=None, memory_refresh="reference",
-                 splitk_reduce="atomic", image_query=None, image_query_lr=None):
+                 splitk_reduce="atomic", image_query=None, image_query_lr=None, optimizer="adam",
+                 schedule_decay=0.004, clipnorm=None):
         self.clip_norm, self.adv_clip_norm = check_args(  # every refusal, before any device call
             net, batch, k, n_samples, mode, precision, rnn_precision, loss_channels, process_group, adversary,
             clip_norm, adv_clip_norm, voiceprint, memory, memory_refresh, splitk_reduce=splitk_reduce,
-            inet=image_query)
+            inet=image_query, optimizer=optimizer, schedule_decay=schedule_decay, clipnorm=clipnorm)
+        self.optimizer, self.schedule_decay = optimizer, float(schedule_decay)
+        self.clipnorm = None if clipnorm is None else float(clipnorm)
         self.inet = image_query
         self.vnet, self.memory, self.memory_refresh, self.adversary = voiceprint, memory, memory_refresh, adversary
         self.align = getattr(net, "attention", "dot") == "align"
@@ -158,9 +170,19 @@ class SepTrainer:
         # {hand-off timed out, refused-update count} (the recurrence kernels set [0]; the guarded
         # Adam counts its refusals in [1])
         self.status = torch.zeros(2, device=dev, dtype=torch.int32)
-        self.opt = adam.GuardedAdam(net.flat, self.status, self.loss, lr, betas, eps, clip_norm=self.clip_norm)
+        okw = dict(kind=optimizer, schedule_decay=schedule_decay, clipnorm=self.clipnorm)
+        query_net = voiceprint if voiceprint is not None else image_query
+        if self.clipnorm is not None and query_net is not None:
+            # the joint norm: one fp64 buffer [parts(net.flat) | parts(encoder.flat)], each optimizer writes its
+            # slice and sums the whole (the same sum, bit for bit, and the same coefficient in both updates)
+            n0 = ops.grad_sumsq_parts(net.flat.numel())
+            joint = torch.zeros(n0 + ops.grad_sumsq_parts(query_net.flat.numel()), dtype=torch.float64, device=dev)
+            okw.update(parts=(joint, 0))
+        self.opt = adam.GuardedAdam(net.flat, self.status, self.loss, lr, betas, eps, clip_norm=self.clip_norm, **okw)
+        if okw.get("parts"):
+            okw.update(parts=(joint, n0))  # (the query encoder's optimizer, below)
         self.m, self.v = self.opt.m, self.opt.v
-        if self.clip_norm is not None:
+        if self.opt.clip is not None:
             self.grad_norm, self._nonfinite = self.opt.grad_norm, self.opt.nonfinite  # (_nonfinite: the tests read it)
         nch = loss_channels if loss_channels else K
         self.s1 = 1.0 / (B * nch * T * F)
@@ -183,14 +205,14 @@ class SepTrainer:
         if voiceprint is not None:
             self.vp = VoiceprintStep(voiceprint, memory, memory_refresh, self.mag_src, self.spk, self.q, self.dq,
                                      self.status, self.loss, lr if voiceprint_lr is None else voiceprint_lr, betas, eps,
-                                     wgrad_split="auto" if splitk_reduce == "fixed" else 1)
+                                     wgrad_split="auto" if splitk_reduce == "fixed" else 1, opt_kw=okw)
             self.vp_enc, self.vp_opt = self.vp.enc, self.vp.opt
         self.images = None
         if image_query is not None:  # the same slot: the trainer calls queries / backward / optimizer_step on either
             self.images = torch.zeros(B, K, image_query.h, image_query.w, **f32)
             self.vp = ImageQueryStep(image_query, memory, memory_refresh, self.images, self.spk, self.q, self.dq,
                                      self.status, self.loss, lr if image_query_lr is None else image_query_lr, betas,
-                                     eps)
+                                     eps, opt_kw=okw)
             self.vp_enc, self.vp_opt = self.vp.enc, self.vp.opt
         if not self.fast:
             return
@@ -829,14 +851,24 @@ class SepTrainer:
         afterwards (device, not synced).  A gradient with an Inf or NaN is refused like a timed-out step and
         counted; check() rolls it out of step_count and adds it to skipped_nonfinite without raising.  The
         Discriminator's updates run first and are guarded by adv_clip_norm alone: a non-finite separation
-        gradient does not undo them."""
+        gradient does not undo them.
+
+        optimizer="nadam": the same launch sequence with dl4ss_nadam, its momentum schedule taken from the step
+        count on the host (adam.nadam_schedule).  clipnorm: the clip by Keras's rule; with a query encoder both
+        sums of squares go into one shared buffer before either update, so the net's and the encoder's updates
+        clip by the one joint norm, and a joint norm that is not finite sets the sticky bit that stops the
+        encoder's update and the memory store behind it (check() raises)."""
         self.wait_allreduce()
         if self.inet is not None:  # a non-finite loss refuses this step's updates and memory store
             self.vp.guard()
         if self.adv is not None:  # the Discriminator's updates first (the reference's order)
             self.adv.optimizer_step()
         shadow = self._shadow if (self._shadow_on and hasattr(self, "_shadow")) else None
-        self.opt.step(self.net.grad, dp_flag=self.net.dp_flag, gscale=1.0 / self.world, shadow=shadow)
+        joint = self.opt.joint  # the joint norm: both sums of squares before either update
+        if joint:
+            self.opt.sumsq(self.net.grad)
+            self.vp.opt.sumsq(self.vp.net.grad)
+        self.opt.step(self.net.grad, dp_flag=self.net.dp_flag, gscale=1.0 / self.world, shadow=shadow, summed=joint)
         # the update bypasses torch's version counter: a new generation of the parameters, whose bf16
         # copies only this trainer holds (written by the same launch), and only if they were current
         # before it -- copies stale before the update stay stale after it
@@ -997,7 +1029,15 @@ class SepTrainer:
         image_query: bit 1 of status[0] is the step's loss guard (dl4ss_imgq_guard: a loss that is not finite).
         The steps it refused -- the one with that loss and every one enqueued behind it -- are taken out of the
         step counts in the same way, the status word is reset and check() raises RuntimeError("non-finite loss
-        ...") when bit 1 alone is set; with bit 0 set as well, the time-out's message."""
+        ...") when bit 1 alone is set; with bit 0 set as well, the time-out's message.
+
+        clipnorm with voiceprint= / image_query= (the joint norm): a joint sum of squares that is not finite sets
+        bit 2 of status[0] (ops.STATUS_NONFINITE_GRAD), sticky in the same way, so that neither optimizer nor the
+        memory store runs; the refused steps leave the step count, are added to skipped_nonfinite, the word is
+        reset and check() raises RuntimeError("non-finite gradient ...").  Without a query encoder clipnorm is
+        counted and skipped exactly as clip_norm is, with no raise.  The bits are tested one by one: a time-out
+        (bit 0) comes first whatever else is set, then bit 2 (also with bit 1 beside it: a step enqueued behind
+        the refusal whose loss was not finite either), then bit 1."""
         torch.cuda.synchronize()
         s, refused = (int(x) for x in self.status.tolist())
         if s or refused:
@@ -1005,11 +1045,21 @@ class SepTrainer:
             # (optimizer, updates per step) on this status word; the voiceprint encoder's steps with the net's count
             opts = [(self.opt, 1)] + ([(self.adv_opt, self.adv.updates)] if self.adv is not None else [])
             timed_out = adam.timed_out_steps(refused, opts + ([(self.vp.opt, 1)] if self.vp is not None else []))
+            skipped = self.opt.skipped_nonfinite
             for opt, n in opts:  # a timed-out step refused the Discriminator's updates too
                 opt.settle(timed_out, n)
             if not (s or timed_out):
                 return
-            if s == 2:  # (bit 1: the image-query step's loss guard, dl4ss_imgq_guard)
+            # status[0] by its bits: 0 a hand-off time-out (first: its workspaces need the reset below), 2 the
+            # non-finite joint gradient norm (sticky), 1 the image-query step's loss guard (dl4ss_imgq_guard)
+            if not s & 1 and s & ops.STATUS_NONFINITE_GRAD:
+                # opt.settle has moved the step with that gradient to skipped_nonfinite; the steps enqueued behind
+                # it, refused by the sticky bit (a later one's loss guard may have added bit 1), are skipped for
+                # the same reason
+                self.opt.skipped_nonfinite += timed_out
+                self.vp.opt.settle(0)
+                raise RuntimeError(f"non-finite gradient: {self.opt.skipped_nonfinite - skipped} update(s) refused")
+            if not s & 1 and s & 2:
                 raise RuntimeError(f"non-finite loss: {timed_out} update(s) refused")
             self.rnn_ws_all.zero_()  # a timed-out launch's half-written hand-offs must not reach the next
             if self.vp is not None:

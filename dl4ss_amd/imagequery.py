@@ -119,11 +119,11 @@ class ImageQueryStep(MemoryQueryStep):
     """The image queries of a training step (SepTrainer(image_query=, memory=)): the encoder over the step's images
     (B, K, h, w), the memory, the encoder's guarded Adam and the memory refresh (voiceprint.MemoryQueryStep)."""
 
-    def __init__(self, inet, memory, refresh, images, spk, q, dq, status, loss, lr, betas, eps):
+    def __init__(self, inet, memory, refresh, images, spk, q, dq, status, loss, lr, betas, eps, opt_kw=None):
         B, K, h, w = images.shape
         self.maps = images.view(B * K, h, w)
         super().__init__(inet, memory, refresh, ImageQueryEncoder(inet, B * K), spk, q, dq, status, loss, lr, betas,
-                         eps)
+                         eps, opt_kw)
 
     def encoder_input(self):
         return self.maps

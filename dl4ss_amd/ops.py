@@ -437,8 +437,70 @@ def check_clip_norm(x, name="clip_norm"):
     return x
 
 
+CLIP_TORCH, CLIP_KERAS = (_lib.OPTIM_CONSTANTS[k] for k in ("DL4SS_CLIP_TORCH", "DL4SS_CLIP_KERAS"))
+CLIP_MAX_PARTS = _lib.OPTIM_CONSTANTS["DL4SS_CLIP_MAX_PARTS"]
+STATUS_NONFINITE_GRAD = _lib.OPTIM_CONSTANTS["DL4SS_STATUS_NONFINITE_GRAD"]  # the sticky bit of status[0]
+
+
+def _clip_args(clip, n, name, n_part=None):
+    """(part, n_part, max_norm, gnorm, nonfinite) of a ``clip`` tuple, checked.  ``n_part`` None: part holds
+    grad_sumsq's partials of the n-element gradient; a number: part's first n_part values, whatever wrote them."""
+    part, max_norm, gnorm, nonfinite = clip
+    max_norm = check_clip_norm(max_norm, f"{name}: max_norm")
+    if n_part is None:
+        n_part = grad_sumsq_parts(n)
+    elif not 1 <= int(n_part) <= CLIP_MAX_PARTS:
+        raise ValueError(f"{name}: 1 <= n_part <= {CLIP_MAX_PARTS}")
+    if part.dtype != torch.float64 or part.numel() < n_part:
+        raise ValueError(f"{name}: clip needs the {n_part} float64 partials of grad_sumsq")
+    if gnorm is not None and (gnorm.dtype != torch.float32 or gnorm.numel() < 2):
+        raise ValueError(f"{name}: gnorm must hold 2 float32 values")
+    if nonfinite.dtype != torch.int32 or nonfinite.numel() < 1:
+        raise ValueError(f"{name}: nonfinite must be an int32 counter")
+    return part, int(n_part), max_norm, gnorm, nonfinite
+
+
+def _clip_kw(clip, n, name, clip_rule, n_part, sticky):
+    """The clip's keywords of the dl4ss_optim.h entry points (clip None: part NULL, unclipped)."""
+    if clip_rule not in (CLIP_TORCH, CLIP_KERAS):
+        raise ValueError(f"{name}: clip_rule {clip_rule!r}, expected {CLIP_TORCH} (torch) or {CLIP_KERAS} (Keras)")
+    if clip is None:
+        return dict(part=None, n_part=0, clip_rule=int(clip_rule), max_norm=0.0, gnorm=None, nonfinite=None,
+                    nonfinite_sticky=0)
+    part, n_part, max_norm, gnorm, nonfinite = _clip_args(clip, n, name, n_part)
+    return dict(part=_lib.ptr(part), n_part=n_part, clip_rule=int(clip_rule), max_norm=max_norm,
+                gnorm=_lib.ptr(gnorm), nonfinite=_lib.ptr(nonfinite), nonfinite_sticky=int(bool(sticky)))
+
+
+def _update_kw(p, g, m, v, step, lr, betas, eps, status, loss, dp_flag, gscale, shadow, name):
+    """The keywords every guarded update shares, shadow segments included (none: nseg 0)."""
+    for t in (p, g, m, v):
+        _f32c(t, name)
+    if status is not None and status.numel() < 2:
+        raise ValueError(f"{name}: the status word needs 2 ints (timed out, refused-update count)")
+    nseg, seg_off, seg_rows, seg_cols, seg_y, seg_ldy = shadow if shadow is not None else (0,) + (None,) * 5
+    return dict(p=_lib.ptr(p), g=_lib.ptr(g), m=_lib.ptr(m), v=_lib.ptr(v), n=p.numel(), lr=float(lr),
+                beta1=float(betas[0]), beta2=float(betas[1]), eps=float(eps), step=int(step),
+                status=_lib.ptr(status), dp_flag=_lib.ptr(dp_flag), gscale=float(gscale), loss=_lib.ptr(loss),
+                nseg=nseg, seg_off=seg_off, seg_rows=seg_rows, seg_cols=seg_cols, seg_y=seg_y, seg_ldy=seg_ldy,
+                stream=_lib.stream_ptr())
+
+
+def nadam_(p, g, m, v, step, schedule, lr=2e-3, betas=(0.9, 0.999), eps=1e-8, status=None, loss=None, dp_flag=None,
+           gscale=1.0, shadow=None, clip=None, clip_rule=CLIP_KERAS, n_part=None, sticky=False):
+    """Keras 1's Nadam step on flat buffers (dl4ss_nadam, include/dl4ss_optim.h has the formulas), arguments as
+    adam_.  ``schedule``: (mu(step), mu(step + 1), P(step)) as Python floats, adam.nadam_schedule's.  ``clip``:
+    adam_'s tuple, by ``clip_rule`` CLIP_KERAS (c = max_norm / nrm where nrm >= max_norm, else 1) or CLIP_TORCH;
+    ``n_part``: part holds that many partials, of this gradient or of several side by side (the joint norm);
+    ``sticky``: a refusal for a non-finite sum also sets bit STATUS_NONFINITE_GRAD of status[0]."""
+    mu, mu_next, mu_prod = (float(x) for x in schedule)
+    kw = _update_kw(p, g, m, v, step, lr, betas, eps, status, loss, dp_flag, gscale, shadow, "nadam_")
+    _lib.call("dl4ss_nadam", mu=mu, mu_next=mu_next, mu_prod=mu_prod,
+              **_clip_kw(clip, p.numel(), "nadam_", clip_rule, n_part, sticky), **kw)
+
+
 def adam_(p, g, m, v, step, lr=2e-4, betas=(0.9, 0.999), eps=1e-8, status=None, loss=None, dp_flag=None, gscale=1.0,
-          shadow=None, clip=None):
+          shadow=None, clip=None, clip_rule=CLIP_TORCH, n_part=None, sticky=False):
     """torch Adam step on flat buffers; with ``status`` (the recurrence hand-off status word,
     2 ints: {timed out, refused-update count}) the update is refused on device when a hand-off
     of this step timed out, loss[0] is set to NaN and status[1] counts the refusal
@@ -450,7 +512,13 @@ def adam_(p, g, m, v, step, lr=2e-4, betas=(0.9, 0.999), eps=1e-8, status=None, 
     ``clip``: (part, max_norm, gnorm, nonfinite) -- the gradient's global norm clipped to max_norm
     (dl4ss_adam_clipped): part = grad_sumsq(g), gnorm a float32[2] that receives {the norm of g * gscale, the
     coefficient c} (or None), nonfinite an int32[1] that counts the updates refused because g held an Inf
-    or NaN (refused like a timed-out step: status[1] counts them too).  None: today's call, unchanged."""
+    or NaN (refused like a timed-out step: status[1] counts them too).  None: today's call, unchanged.
+    ``clip_rule`` CLIP_KERAS, ``n_part`` or ``sticky`` (nadam_'s): dl4ss_adam_clipped_ex; without them every call
+    reaches the entry point it always reached, with the same arguments."""
+    if clip is not None and (clip_rule != CLIP_TORCH or n_part is not None or sticky):
+        kw = _update_kw(p, g, m, v, step, lr, betas, eps, status, loss, dp_flag, gscale, shadow, "adam_")
+        _lib.call("dl4ss_adam_clipped_ex", **_clip_kw(clip, p.numel(), "adam_", clip_rule, n_part, sticky), **kw)
+        return
     for t in (p, g, m, v):
         _f32c(t, "adam")
     if status is not None and status.numel() < 2:

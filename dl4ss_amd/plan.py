@@ -14,12 +14,29 @@ def _same_device(net, other):
     return (other.device.type, other.device.index or 0) == (net.device.type, net.device.index or 0)
 
 
+def check_optimizer(optimizer, schedule_decay, clip_norm, clipnorm):
+    """The optimizer's arguments of a trainer (SepTrainer, ClassifierTrainer): returns clipnorm as a float or None."""
+    if optimizer not in ("adam", "nadam"):
+        raise ValueError(f"optimizer {optimizer!r}: expected 'adam' or 'nadam'")
+    if not float(schedule_decay) >= 0.0:  # also NaN
+        raise ValueError(f"schedule_decay must not be negative, got {schedule_decay}")
+    if clipnorm is None:
+        return None
+    if clip_norm is not None:
+        raise ValueError("clip_norm (torch.nn.utils.clip_grad_norm_'s rule) and clipnorm (Keras's rule) are given "
+                         "together: choose one")
+    return ops.check_clip_norm(clipnorm, "clipnorm")
+
+
 def check_args(net, batch, k, n_samples, mode, precision, rnn_precision, loss_channels, process_group, adversary,
-               clip_norm, adv_clip_norm, vnet, memory, memory_refresh, splitk_reduce="atomic", inet=None):
+               clip_norm, adv_clip_norm, vnet, memory, memory_refresh, splitk_reduce="atomic", inet=None,
+               optimizer="adam", schedule_decay=0.004, clipnorm=None):
     """Every combination of SepTrainer's arguments it is not built for, each refused with its reason: host checks
-    only, run in front of the first device call.  Returns the clip thresholds as floats (or None)."""
+    only, run in front of the first device call.  Returns the clip thresholds as floats (or None); ``clipnorm``
+    (Keras's rule) is checked here and stays the caller's."""
     if mode not in ("label", "pit", "crm"):
         raise ValueError(mode)
+    check_optimizer(optimizer, schedule_decay, clip_norm, clipnorm)
     if splitk_reduce not in ("atomic", "fixed"):
         raise ValueError(f"splitk_reduce {splitk_reduce!r}: expected 'atomic' or 'fixed'")
     if splitk_reduce == "fixed" and precision != "fp32":

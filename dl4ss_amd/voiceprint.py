@@ -205,13 +205,14 @@ class MemoryQueryStep:
     and says what it reads (``encoder_input``).  ``spk``, ``q``, ``dq``, ``status``, ``loss``: the trainer's
     buffers (the trainer itself is not referenced: _ws_slot)."""
 
-    def __init__(self, net, memory, refresh, enc, spk, q, dq, status, loss, lr, betas, eps):
+    def __init__(self, net, memory, refresh, enc, spk, q, dq, status, loss, lr, betas, eps, opt_kw=None):
         n = spk.numel()
         f32 = dict(device=net.device, dtype=torch.float32)
         self.net, self.memory, self.refresh, self.enc, self.status = net, memory, refresh, enc, status
         self.spk, self.q, self.dq = spk.view(-1), q, dq.view(n, -1)
         self.u, self.dv, self.q2 = (torch.empty(n, net.E, **f32) for _ in range(3))  # q2: the refreshed rows
-        self.opt = GuardedAdam(net.flat, status, loss, lr, betas, eps)
+        # opt_kw: the trainer's optimizer= / schedule_decay= / clipnorm= (with parts=: the joint norm's buffer)
+        self.opt = GuardedAdam(net.flat, status, loss, lr, betas, eps, **(opt_kw or {}))
 
     def encoder_input(self):
         raise NotImplementedError
@@ -230,7 +231,7 @@ class MemoryQueryStep:
     def optimizer_step(self, step):
         """The encoder's guarded Adam at the mask net's count ``step`` (refused with the net's), then the memory
         refresh, skipped on device with a refused update: "reference" re-encodes first (nnet.py:131-135)."""
-        self.opt.step(self.net.grad, step=step)
+        self.opt.step(self.net.grad, step=step, summed=self.opt.joint)
         q = self.q
         if self.refresh == "reference":
             q = self.q2
@@ -250,12 +251,13 @@ class VoiceprintStep(MemoryQueryStep):
     pairs: a silent frame that shares its transform with a voiced one -- the first silent frame behind an odd
     number of voiced ones -- carries that neighbour's rounding residue, ~1e-8 of it, and counts as valid.)"""
 
-    def __init__(self, vnet, memory, refresh, mag_src, spk, q, dq, status, loss, lr, betas, eps, wgrad_split=1):
+    def __init__(self, vnet, memory, refresh, mag_src, spk, q, dq, status, loss, lr, betas, eps, wgrad_split=1,
+                 opt_kw=None):
         B, K, T, F = mag_src.shape
         self.maps = mag_src.view(B * K, T, F)
         # its recurrences share the step's status word
         enc = VoiceprintEncoder(vnet, B * K, T, status=status, wgrad_split=wgrad_split)
-        super().__init__(vnet, memory, refresh, enc, spk, q, dq, status, loss, lr, betas, eps)
+        super().__init__(vnet, memory, refresh, enc, spk, q, dq, status, loss, lr, betas, eps, opt_kw)
 
     def encoder_input(self):
         return self.maps
