@@ -26,9 +26,11 @@ def _check_status(status, what):
         raise RuntimeError(f"{what}: BiRNN hand-off timed out (status {s})")
 
 
-def birnn_fwd_impl(x, w_ih, b_ih, w_hh, b_hh, cell, H, precision):
+def birnn_fwd_impl(x, w_ih, b_ih, w_hh, b_hh, cell, H, precision, gates="logistic"):
     """One bidirectional layer's forward: (out (B,T,2H), hprev, act, cs or None).  Shared by
-    BiRNNLayerFn and the dl4ss::birnn_layer custom op (dl4ss_amd.library)."""
+    BiRNNLayerFn and the dl4ss::birnn_layer / dl4ss::keras_lstm_layer custom ops (dl4ss_amd.library).
+    gates "hard": Keras 1's LSTM cell (ops.HARD_GATES; fp32 LSTM only)."""
+    flags = ops.gate_flags(gates, cell, precision)
     x = _c(x)
     B, T, D = x.shape
     cid = CELLS[cell]
@@ -42,7 +44,7 @@ def birnn_fwd_impl(x, w_ih, b_ih, w_hh, b_hh, cell, H, precision):
     ws = torch.empty((wsn + 7) // 8, dtype=torch.int64, device=dev)
     status = torch.zeros(1, dtype=torch.int32, device=dev)
     ops.birnn_fwd(cell, B, T, H, G=G, w_hh=_c(w_hh), b_hh=_c(b_hh), out=out, hprev=hprev, act=act, cs=cs, ws=ws,
-                  ws_bytes=wsn, status=status, precision=precision)
+                  ws_bytes=wsn, status=status, precision=precision, flags=flags)
     _check_status(status, "dl4ss_birnn_fwd")
     return out, hprev, act, cs
 
@@ -54,8 +56,10 @@ def _birnn_ws_bytes(cid, B, H):
     return wsn
 
 
-def birnn_bwd_impl(dout, x, w_ih, w_hh, hprev, act, cs, cell, H, precision, need_dx=True):
-    """BPTT + the layer's weight / bias / input gradients: (dx or None, dw_ih, db_ih, dw_hh, db_hh)."""
+def birnn_bwd_impl(dout, x, w_ih, w_hh, hprev, act, cs, cell, H, precision, need_dx=True, gates="logistic"):
+    """BPTT + the layer's weight / bias / input gradients: (dx or None, dw_ih, db_ih, dw_hh, db_hh).
+    gates: as birnn_fwd_impl (act must come from a forward of the same setting)."""
+    flags = ops.gate_flags(gates, cell, precision)
     B, T, D = x.shape
     dev = x.device
     NGH = (4 if cell == "lstm" else 3) * H
@@ -67,7 +71,7 @@ def birnn_bwd_impl(dout, x, w_ih, w_hh, hprev, act, cs, cell, H, precision, need
     status = torch.zeros(1, dtype=torch.int32, device=dev)
     # (one entry point for every H: the H = 600 classifier runs its large-hidden BPTT, the generic kernel)
     ops.birnn_bwd(cell, B, T, H, dOut=dout, w_hh=_c(w_hh), act=act, cs=cs if cell == "lstm" else None, hprev=hprev,
-                  dG=dG, dGh=dGh, ws=ws, ws_bytes=wsn, status=status, precision=precision)
+                  dG=dG, dGh=dGh, ws=ws, ws_bytes=wsn, status=status, precision=precision, flags=flags)
     _check_status(status, "dl4ss_birnn_bwd")
     dGh = dG if dGh is None else dGh
     w_ih = _c(w_ih)
@@ -94,23 +98,29 @@ class BiRNNLayerFn(torch.autograd.Function):
     forward direction's rows first (G = 4 LSTM / 3 GRU)  ->  out (B,T,2H) = [fwd | rev].
     Replaces one layer of nn.LSTM / nn.GRU(batch_first, bidirectional)
     (TDAA_beta/main_run_sstune_EvalVer.py:282-293, Torch_multi/main_run.py:263-273).
+    gates "hard": Keras 1's LSTM cell instead (hard_sigmoid i / f / o gates; one layer of
+    Bidirectional(LSTM(...)) at DL4SS_Keras/nnet.py:51-68), fp32 LSTM only.
     """
 
     @staticmethod
-    def forward(ctx, x, w_ih, b_ih, w_hh, b_hh, cell, H, precision):
-        out, hprev, act, cs = birnn_fwd_impl(x, w_ih, b_ih, w_hh, b_hh, cell, H, precision)
+    def forward(ctx, x, w_ih, b_ih, w_hh, b_hh, cell, H, precision, *gates):  # gates: optional, "logistic"
+        if len(gates) > 1:
+            raise TypeError("BiRNNLayerFn.apply(x, w_ih, b_ih, w_hh, b_hh, cell, H, precision[, gates])")
+        g = gates[0] if gates else "logistic"
+        out, hprev, act, cs = birnn_fwd_impl(x, w_ih, b_ih, w_hh, b_hh, cell, H, precision, g)
         ctx.save_for_backward(_c(x), _c(w_ih), _c(w_hh), hprev, act, cs if cs is not None else act)
-        ctx.meta = (cell, H, precision)
+        ctx.meta = (cell, H, precision, g)
+        ctx.n_opt = len(gates)  # backward returns one gradient per argument apply() was given
         return out
 
     @staticmethod
     def backward(ctx, dout):
         x, w_ih, w_hh, hprev, act, cs = ctx.saved_tensors
-        cell, H, precision = ctx.meta
+        cell, H, precision, gates = ctx.meta
         dx, dw_ih, db_ih, dw_hh, db_hh = birnn_bwd_impl(dout, x, w_ih, w_hh, hprev, act,
                                                         cs if cell == "lstm" else None, cell, H, precision,
-                                                        bool(ctx.needs_input_grad[0]))
-        return dx, dw_ih, db_ih, dw_hh, db_hh, None, None, None
+                                                        bool(ctx.needs_input_grad[0]), gates)
+        return (dx, dw_ih, db_ih, dw_hh, db_hh, None, None, None) + (None,) * ctx.n_opt
 
 
 def linear_tanh_bwd_impl(dv, x2d, w, v, precision, need_dx=True):

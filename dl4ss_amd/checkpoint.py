@@ -127,7 +127,9 @@ def save_reference_discriminator(module, tag, epoch, directory="params"):
 
 def save_reference_params(net, directory, tag, epoch):
     """Write the reference's file layout ``param_{tag}_{hidden3d,emblayer,adjlayer}_{epoch}``, and
-    ``param_{tag}_attlayer_{epoch}`` for a net that has the 'align' attention weights."""
+    ``param_{tag}_attlayer_{epoch}`` for a net that has the 'align' attention weights.  These files are plain
+    state dicts of tensors under the reference's keys and have no place for metadata: ``net.gates`` is NOT
+    written, so whoever loads them into a SepNet must build it with the ``gates`` the weights were trained with."""
     os.makedirs(directory, exist_ok=True)
     paths = {}
     for kind, pre in PREFIX.items():
@@ -142,16 +144,25 @@ def save_reference_params(net, directory, tag, epoch):
 
 def save_voiceprint(path, vnet, memory):
     """The voiceprint encoder's parameters (``spk.layer.*``) and the speaker memory in one file: plain
-    ``torch.save`` of the two state dicts (the Keras tree's weights have no torch layout to mirror)."""
+    ``torch.save`` of the two state dicts (the Keras tree's weights have no torch layout to mirror), and beside
+    them the encoder's cell form ``vnet.gates`` ("logistic" or "hard") as a plain string."""
     torch.save({"voiceprint": {k: v.cpu() for k, v in vnet.state_dict().items()},
-                "memory": {k: v.cpu() for k, v in memory.state_dict().items()}}, path)
+                "memory": {k: v.cpu() for k, v in memory.state_dict().items()},
+                "gates": str(getattr(vnet, "gates", "logistic"))}, path)
 
 
 def load_voiceprint(path, vnet, memory):
-    """Load a save_voiceprint file into ``vnet`` and ``memory`` (in place; shapes must match)."""
+    """Load a save_voiceprint file into ``vnet`` and ``memory`` (in place; shapes must match).  The file's
+    ``gates`` (a file from before the field: "logistic") must be ``vnet.gates``: weights trained through one cell
+    form are not weights of the other, so a mismatch raises ValueError before anything is written."""
     sd = torch.load(path, map_location="cpu", weights_only=True)
-    if not isinstance(sd, dict) or set(sd) != {"voiceprint", "memory"}:
+    if not isinstance(sd, dict) or set(sd) - {"gates"} != {"voiceprint", "memory"}:
         raise ValueError(f"{path}: not a save_voiceprint file")
+    gates, own = sd.get("gates", "logistic"), getattr(vnet, "gates", "logistic")
+    if gates not in ("logistic", "hard"):
+        raise ValueError(f"{path}: gates {gates!r}, expected 'logistic' or 'hard'")
+    if gates != own:
+        raise ValueError(f"{path}: saved from an encoder with gates={gates!r}, this VoiceprintNet has gates={own!r}")
     for name, shape in vnet.specs:
         if name not in sd["voiceprint"] or tuple(sd["voiceprint"][name].shape) != tuple(shape):
             raise ValueError(f"{path}: {name} missing or not of shape {tuple(shape)}")
@@ -181,3 +192,72 @@ def load_image_query(path, inet, memory):
         raise ValueError(f"{path}: mem missing or not of shape {(memory.M, memory.E)}")
     inet.load_state_dict(sd["image_query"])
     memory.load_state_dict(sd["memory"])
+
+
+# --------------------------------------------------------------------------- Keras 1's LSTM weights
+KERAS_GATES = ("i", "f", "c", "o")  # this project's row blocks [i | f | g | o]; Keras names the candidate g "c"
+KERAS_LSTM_NAMES = tuple(f"{k}_{g}" for g in KERAS_GATES for k in ("W", "U", "b"))
+
+
+def _keras_layer(net, layer, direction):
+    if getattr(net, "gates", "logistic") != "hard":
+        raise ValueError("Keras 1's LSTM weights belong to a net with gates='hard' (its cell), this net has "
+                         f"gates={getattr(net, 'gates', 'logistic')!r}")
+    if not 0 <= int(layer) < net.L:
+        raise ValueError(f"layer {layer}: the net has layers 0..{net.L - 1}")
+    if direction not in ("forward", "backward"):
+        raise ValueError(f"direction {direction!r}: expected 'forward' or 'backward'")
+    sfx = f"_l{int(layer)}" + ("_reverse" if direction == "backward" else "")
+    return {kind: net.view(f"{net.layer_prefix}{kind}{sfx}") for kind in ("weight_ih", "weight_hh", "bias_ih",
+                                                                         "bias_hh")}
+
+
+def load_keras_lstm(net, layer, direction, weights):
+    """One direction of one layer of Keras 1's ``Bidirectional(LSTM(...))`` (DL4SS_Keras/nnet.py:51-68) into a
+    ``SepNet`` or ``VoiceprintNet`` built with ``gates="hard"`` (in place).  ``direction``: "forward" or "backward"
+    (the wrapper's two LSTMs; "backward" is this project's ``_reverse``).  ``weights`` maps Keras 1's per-gate
+    names to arrays (numpy or torch): ``W_i, U_i, b_i, W_f, U_f, b_f, W_c, U_c, b_c, W_o, U_o, b_o`` with
+    ``W_*`` (in, H), ``U_*`` (H, H), ``b_*`` (H,).  The mapping is by NAME, never by list position (Keras 1.x
+    releases order ``get_weights()`` differently): ``weight_ih`` rows [i | f | g (Keras's c) | o] = ``W_*^T``,
+    ``weight_hh`` = ``U_*^T``, ``bias_ih`` = ``b_*``, ``bias_hh`` = 0 (Keras has one bias).  Every name must be
+    present with the layer's shape, and no other; nothing is written before all are checked.  Reading the arrays
+    out of an ``.h5`` file is the caller's (h5py is not a dependency)."""
+    p = _keras_layer(net, layer, direction)
+    H, D = net.H, p["weight_ih"].shape[1]
+    if set(weights) != set(KERAS_LSTM_NAMES):
+        raise ValueError(f"weights: names {sorted(weights)} are not Keras 1's {sorted(KERAS_LSTM_NAMES)}")
+    want = {"W": (D, H), "U": (H, H), "b": (H,)}
+    t = {}
+    for name in KERAS_LSTM_NAMES:
+        t[name] = torch.as_tensor(weights[name]).detach().to("cpu", torch.float32)
+        if tuple(t[name].shape) != want[name[0]]:
+            raise ValueError(f"weights: {name} has shape {tuple(t[name].shape)}, the layer expects {want[name[0]]}")
+    for q, g in enumerate(KERAS_GATES):
+        rows = slice(q * H, (q + 1) * H)
+        p["weight_ih"][rows].copy_(t[f"W_{g}"].t())
+        p["weight_hh"][rows].copy_(t[f"U_{g}"].t())
+        p["bias_ih"][rows].copy_(t[f"b_{g}"])
+    p["bias_hh"].zero_()
+    if hasattr(net, "params_changed"):
+        net.params_changed()
+    return net
+
+
+def export_keras_lstm(net, layer, direction):
+    """The inverse of load_keras_lstm: a dict of the twelve per-gate arrays (CPU fp32 tensors) of one direction of
+    one layer of a ``gates="hard"`` net.  Keras's cell has one bias, so ``bias_hh`` must be exactly zero (as
+    load_keras_lstm leaves it): a layer trained here with both biases is refused rather than folded silently --
+    add ``bias_hh`` into ``bias_ih`` and zero it first (the cell's sum b_ih + b_hh is unchanged up to one
+    rounding)."""
+    p = _keras_layer(net, layer, direction)
+    H = net.H
+    if bool((p["bias_hh"] != 0).any()):
+        raise ValueError("export_keras_lstm: bias_hh is not zero; Keras's LSTM has one bias (fold bias_hh into "
+                         "bias_ih and zero it first)")
+    out = {}
+    for q, g in enumerate(KERAS_GATES):
+        rows = slice(q * H, (q + 1) * H)
+        out[f"W_{g}"] = p["weight_ih"][rows].detach().cpu().t().contiguous()
+        out[f"U_{g}"] = p["weight_hh"][rows].detach().cpu().t().contiguous()
+        out[f"b_{g}"] = p["bias_ih"][rows].detach().cpu().clone()
+    return out

@@ -8,7 +8,7 @@ using namespace dl4ss_rnn;
 
 namespace {
 
-// (the precision flags DL4SS_RNN_WS_ZEROED / _DGH_PAD8 / _DEFER_BIAS / _DOUT_SLABS are the public header's)
+// (the precision flags DL4SS_RNN_WS_ZEROED / _DGH_PAD8 / _DEFER_BIAS / _HARD_GATES / _DOUT_SLABS are the public header's)
 constexpr unsigned SPIN_LIMIT = 1u << 20;  // ~1 s of polling: a stuck hand-off exits, never hangs
 
 struct Plan {
@@ -23,9 +23,10 @@ struct Plan {
   long long groups() const { return 2LL * nchunk; }
   // dynamic LDS of each kernel (birnn_layout.h); mf: the bf16 MFMA matvec; xw: the fused input projection
   size_t smem_fwd(bool mf) const { return fwd_lds_bytes(mf, hm(), BC, J, R(), HP, KP); }
-  size_t smem_bwd(bool mf) const {
-    int rpln, kgln;
-    bwd_dims(RPL, KGL, rpln, kgln, big);
+  // hard: the hard-gates cell runs the runtime-bounds BPTT whatever the plan (the generic maxima)
+  size_t smem_bwd(bool mf, bool hard = false) const {
+    int rpln = RPLMAX, kgln = KGLMAX;
+    if (!hard) bwd_dims(RPL, KGL, rpln, kgln, big);
     return bwd_lds_bytes(mf, hm(), BC, J, NG, RP, RP * rpln, KG * kgln);
   }
   size_t smem_fwd_pk(bool xw) const { return fwd_pk_lds_bytes(BC, R(), xw); }
@@ -120,10 +121,12 @@ void fill_args(RnnArgs& a, const Plan& p, int B, int T, int H) {
 }
 
 // one recurrence launch of a plan through its kernel file's entry (pk: the packed kernels, bf16 only)
-int launch(bool fwd, bool mf, bool pk, const Plan& p, const RnnArgs& a, size_t smem, hipStream_t st) {
+// hard: Keras 1's hard_sigmoid gates (generic fp32 LSTM kernels only)
+int launch(bool fwd, bool mf, bool pk, const Plan& p, const RnnArgs& a, size_t smem, hipStream_t st, bool hard = false) {
   const int grid = (int)(p.groups() * p.NG);
-  const int e = fwd ? (pk ? launch_fwd_pk(a, p.cell, p.BC, grid, smem, st) : launch_fwd(a, p.cell, p.BC, mf, grid, smem, st))
-                    : (pk ? launch_bwd_pk(a, p.cell, p.BC, grid, smem, st) : launch_bwd(a, p.cell, p.BC, mf, grid, smem, st));
+  if (hard && (pk || mf)) return (int)hipErrorInvalidValue;
+  const int e = fwd ? (pk ? launch_fwd_pk(a, p.cell, p.BC, grid, smem, st) : launch_fwd(a, p.cell, p.BC, mf, hard, grid, smem, st))
+                    : (pk ? launch_bwd_pk(a, p.cell, p.BC, grid, smem, st) : launch_bwd(a, p.cell, p.BC, mf, hard, grid, smem, st));
   if (e) return e;
   DL4SS_CHECK_LAUNCH();
   return 0;
@@ -279,8 +282,10 @@ DL4SS_API int dl4ss_birnn_fwd_mean(int cell, int precision, int B, int T, int H,
                                    void* stream) {
   DL4SS_REQUIRE(cell == CELL_LSTM || cell == CELL_GRU);
   const bool prezeroed = precision & DL4SS_RNN_WS_ZEROED;  // the caller zeroed the workspace (one fill per step)
-  precision &= ~DL4SS_RNN_WS_ZEROED;
+  const bool hard = precision & DL4SS_RNN_HARD_GATES;  // Keras 1's cell: fp32 LSTM, generic kernel, no bf16 extras
+  precision &= ~(DL4SS_RNN_WS_ZEROED | DL4SS_RNN_HARD_GATES);
   DL4SS_REQUIRE(precision == 0 || precision == 1);
+  DL4SS_REQUIRE(!hard || (cell == CELL_LSTM && precision == 0 && out && !out_bf16 && !hprev_bf16 && !h_mean));
   DL4SS_REQUIRE(B > 0 && T > 0 && H > 0 && G && W_hh && b_hh && (out || out_bf16) && act && workspace && status);
   DL4SS_REQUIRE(cell == CELL_GRU || cs);
   Plan p;
@@ -292,7 +297,7 @@ DL4SS_API int dl4ss_birnn_fwd_mean(int cell, int precision, int B, int T, int H,
     const long long GH = (cell == CELL_LSTM ? 4LL : 3LL) * H;
     for (int b0 = 0; b0 < B; b0 += bs) {
       const long long r = (long long)b0 * T;  // (b, t) rows before the sub-batch
-      const int rc = dl4ss_birnn_fwd_mean(cell, 0, B - b0 < bs ? B - b0 : bs, T, H, G + r * 2 * GH, W_hh, b_hh,
+      const int rc = dl4ss_birnn_fwd_mean(cell, hard ? DL4SS_RNN_HARD_GATES : 0, B - b0 < bs ? B - b0 : bs, T, H, G + r * 2 * GH, W_hh, b_hh,
                                           out + r * 2 * H, hprev ? hprev + r * 2 * H : nullptr, act + r * 2 * 4 * H,
                                           cs ? cs + r * 2 * H : nullptr, nullptr, nullptr, nullptr, workspace,
                                           ws_bytes, status, stream);
@@ -325,7 +330,7 @@ DL4SS_API int dl4ss_birnn_fwd_mean(int cell, int precision, int B, int T, int H,
   a.xbuf = reinterpret_cast<unsigned long long*>(workspace);
   a.gctl = pk ? reinterpret_cast<unsigned*>(static_cast<char*>(workspace) + ctl_offset(p, H)) : nullptr;
   a.status = status;
-  return launch(true, mf, pk, p, a, pk ? p.smem_fwd_pk(false) : p.smem_fwd(mf), st);
+  return launch(true, mf, pk, p, a, pk ? p.smem_fwd_pk(false) : p.smem_fwd(mf), st, hard);
 }
 
 // 1 when the packed bf16 forward (the only one with the fused input projection) applies to
@@ -424,9 +429,11 @@ DL4SS_API int dl4ss_birnn_bwd_ex(int cell, int precision, int B, int T, int H, c
   const bool prezeroed = precision & DL4SS_RNN_WS_ZEROED;
   const bool dgh_pad8 = precision & DL4SS_RNN_DGH_PAD8;
   const bool defer_bias = precision & DL4SS_RNN_DEFER_BIAS;
+  const bool hard = precision & DL4SS_RNN_HARD_GATES;  // Keras 1's cell: fp32 LSTM, generic kernel, no bf16 extras
   const int dout_ns = ((precision & DL4SS_RNN_DOUT_SLABS_MASK) >> 12) + 1;
-  precision &= ~(DL4SS_RNN_WS_ZEROED | DL4SS_RNN_DGH_PAD8 | DL4SS_RNN_DEFER_BIAS | DL4SS_RNN_DOUT_SLABS_MASK);
+  precision &= ~(DL4SS_RNN_WS_ZEROED | DL4SS_RNN_DGH_PAD8 | DL4SS_RNN_DEFER_BIAS | DL4SS_RNN_HARD_GATES | DL4SS_RNN_DOUT_SLABS_MASK);
   DL4SS_REQUIRE(precision == 0 || precision == 1);
+  DL4SS_REQUIRE(!hard || (cell == CELL_LSTM && precision == 0 && dout_ns == 1 && dG && !dG_bf16 && !dGh_bf16));
   DL4SS_REQUIRE(B > 0 && T > 0 && H > 0 && H <= HMAX_L && W_hh && act && workspace && status);
   // the classifier's top layer: its only gradient is d(mean_t h), so dOut may be NULL (read as zero) when
   // dOut_bcast is given -- in the generic kernel (every H > HMAX plan), checked below
@@ -443,7 +450,7 @@ DL4SS_API int dl4ss_birnn_bwd_ex(int cell, int precision, int B, int T, int H, c
     const long long GH = (cell == CELL_LSTM ? 4LL : 3LL) * H;
     for (int b0 = 0; b0 < B; b0 += bs) {
       const long long r = (long long)b0 * T;  // (b, t) rows before the sub-batch
-      const int rc = dl4ss_birnn_bwd_ex(cell, 0, B - b0 < bs ? B - b0 : bs, T, H, dOut ? dOut + r * 2 * H : nullptr,
+      const int rc = dl4ss_birnn_bwd_ex(cell, hard ? DL4SS_RNN_HARD_GATES : 0, B - b0 < bs ? B - b0 : bs, T, H, dOut ? dOut + r * 2 * H : nullptr,
                                         dOut_bcast ? dOut_bcast + (long long)b0 * 2 * H : nullptr, W_hh,
                                         act + r * 2 * 4 * H, cs ? cs + r * 2 * H : nullptr,
                                         hprev ? hprev + r * 2 * H : nullptr, dG + r * 2 * GH,
@@ -485,7 +492,7 @@ DL4SS_API int dl4ss_birnn_bwd_ex(int cell, int precision, int B, int T, int H, c
   const bool bias = pk && (db_ih || db_hh);
   a.dbpart = bias ? reinterpret_cast<float*>(static_cast<char*>(workspace) + handoff_bytes(p, H)) : nullptr;
   a.status = status;
-  const int e = launch(false, mf, pk, p, a, pk ? p.smem_bwd_pk() : p.smem_bwd(mf), st);
+  const int e = launch(false, mf, pk, p, a, pk ? p.smem_bwd_pk() : p.smem_bwd(mf, hard), st, hard);
   if (e || !bias || defer_bias) return e;
   const int GH = (cell == CELL_LSTM ? 4 : 3) * H;
   BiasJobs j{};

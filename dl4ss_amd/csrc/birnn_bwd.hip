@@ -20,8 +20,12 @@ namespace dl4ss_rnn {
 // HM: the largest hidden size of the instantiation (sizes the per-thread offset arrays, the MFMA unit
 // tiles per wave and the MFMA path's transpose area): HMAX for the mask nets, HMAX_L for the H = 600
 // speaker classifier (test_multi_labels_speech.py:240-246,444).
-template <int CELL, int BC, int RPL_T, int KGL_T, bool MF, int HM = HMAX>
+// HARD = true: Keras 1's LSTM cell (DL4SS_RNN_HARD_GATES): the i, f and o gate derivatives are
+// hard_sigmoid's, taken from the saved (clipped) activation (hsig_grad of birnn_common.h), in place of
+// s (1 - s).  fp32 LSTM, runtime-bounds instantiations only.
+template <int CELL, int BC, int RPL_T, int KGL_T, bool MF, int HM = HMAX, bool HARD = false>
 __global__ __launch_bounds__(NT, 1) void rnn_bwd_kernel(RnnArgs a) {
+  static_assert(!HARD || (CELL == CELL_LSTM && !MF && RPL_T == 0 && KGL_T == 0), "hard gates: fp32 LSTM, runtime bounds");
   constexpr int NGATE = CELL == CELL_LSTM ? 4 : 3;
   constexpr int RPLN = MF ? 1 : (RPL_T > 0 ? RPL_T : RPLMAX);  // rows per thread (compile-time)
   constexpr int KGLN = MF ? 1 : (KGL_T > 0 ? KGL_T : KGLMAX);  // k per thread (compile-time)
@@ -265,10 +269,17 @@ __global__ __launch_bounds__(NT, 1) void rnn_bwd_kernel(RnnArgs a) {
           const float ig = act[0], fg = act[1], gg = act[2], og = act[3];
           const float tc = ftanh(c);
           const float dc = dc_next + dh * og * (1.0f - tc * tc);
-          dgi[0] = dc * gg * ig * (1.0f - ig);
-          dgi[1] = dc * cprev * fg * (1.0f - fg);
-          dgi[2] = dc * ig * (1.0f - gg * gg);
-          dgi[3] = dh * tc * og * (1.0f - og);
+          if constexpr (HARD) {
+            dgi[0] = dc * gg * hsig_grad(ig);
+            dgi[1] = dc * cprev * hsig_grad(fg);
+            dgi[2] = dc * ig * (1.0f - gg * gg);
+            dgi[3] = dh * tc * hsig_grad(og);
+          } else {
+            dgi[0] = dc * gg * ig * (1.0f - ig);
+            dgi[1] = dc * cprev * fg * (1.0f - fg);
+            dgi[2] = dc * ig * (1.0f - gg * gg);
+            dgi[3] = dh * tc * og * (1.0f - og);
+          }
           dc_next = dc * fg;
 #pragma unroll
           for (int q = 0; q < NGATE; ++q) dgh[q] = dgi[q];
@@ -346,10 +357,19 @@ __global__ __launch_bounds__(NT, 1) void rnn_bwd_kernel(RnnArgs a) {
 
 namespace {
 template <int CELL, int BC>
-int launch_bwd_t(const RnnArgs& a, bool mf, int grid, size_t smem, hipStream_t st) {
+int launch_bwd_t(const RnnArgs& a, bool mf, bool hard, int grid, size_t smem, hipStream_t st) {
 #ifdef RNN_EXP_MINIMAL
   return (int)hipErrorNotSupported;
 #else
+  if (hard) {  // Keras 1's cell: fp32 LSTM at the runtime-bounds instantiations only (the caller sized smem for them)
+    if constexpr (CELL == CELL_LSTM) {
+      if (mf) return (int)hipErrorInvalidValue;
+      if (a.H > HMAX) return launch_resident(rnn_bwd_kernel<CELL, BC, 0, 0, false, HMAX_L, true>, grid, smem, st, a);
+      return launch_resident(rnn_bwd_kernel<CELL, BC, 0, 0, false, HMAX, true>, grid, smem, st, a);
+    } else {
+      return (int)hipErrorInvalidValue;
+    }
+  }
   int rpln, kgln;
   bwd_dims(a.RPL, a.KGL, rpln, kgln, a.H > HMAX);
   if (a.H > HMAX) {  // large-H instantiations (the H = 600 classifier)
@@ -368,20 +388,20 @@ int launch_bwd_t(const RnnArgs& a, bool mf, int grid, size_t smem, hipStream_t s
 #endif
 }
 template <int CELL>
-int launch_bwd_c(const RnnArgs& a, int BC, bool mf, int grid, size_t smem, hipStream_t st) {
+int launch_bwd_c(const RnnArgs& a, int BC, bool mf, bool hard, int grid, size_t smem, hipStream_t st) {
   switch (BC) {
-    case 1: return launch_bwd_t<CELL, 1>(a, mf, grid, smem, st);
-    case 2: return launch_bwd_t<CELL, 2>(a, mf, grid, smem, st);
-    case 4: return launch_bwd_t<CELL, 4>(a, mf, grid, smem, st);
-    case 8: return launch_bwd_t<CELL, 8>(a, mf, grid, smem, st);
+    case 1: return launch_bwd_t<CELL, 1>(a, mf, hard, grid, smem, st);
+    case 2: return launch_bwd_t<CELL, 2>(a, mf, hard, grid, smem, st);
+    case 4: return launch_bwd_t<CELL, 4>(a, mf, hard, grid, smem, st);
+    case 8: return launch_bwd_t<CELL, 8>(a, mf, hard, grid, smem, st);
     default: return (int)hipErrorInvalidValue;
   }
 }
 }  // namespace
 
-int launch_bwd(const RnnArgs& a, int cell, int BC, bool mf, int grid, size_t smem, hipStream_t st) {
-  return cell == CELL_LSTM ? launch_bwd_c<CELL_LSTM>(a, BC, mf, grid, smem, st)
-                           : launch_bwd_c<CELL_GRU>(a, BC, mf, grid, smem, st);
+int launch_bwd(const RnnArgs& a, int cell, int BC, bool mf, bool hard, int grid, size_t smem, hipStream_t st) {
+  return cell == CELL_LSTM ? launch_bwd_c<CELL_LSTM>(a, BC, mf, hard, grid, smem, st)
+                           : launch_bwd_c<CELL_GRU>(a, BC, mf, hard, grid, smem, st);
 }
 
 }  // namespace dl4ss_rnn

@@ -100,6 +100,13 @@ __device__ __forceinline__ float ftanh(float x) {
   return 2.0f * __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(x * -2.88539008177792681472f)) - 1.0f;
 }
 
+// Keras 1's inner_activation (Theano's hard_sigmoid: slope 0.2, shift 0.5, clip to [0, 1]) of the
+// hard-gates LSTM cell: one FMA whose result is clamped (the `clamp` output modifier, no compare chain)
+__device__ __forceinline__ float hsig(float x) { return fminf(fmaxf(fmaf(0.2f, x, 0.5f), 0.0f), 1.0f); }
+// its derivative from the saved activation s = hsig(x), as the logistic form takes s (1 - s): 0.2 strictly
+// inside the clip, 0 on it
+__device__ __forceinline__ float hsig_grad(float s) { return (s > 0.0f && s < 1.0f) ? 0.2f : 0.0f; }
+
 typedef short bf16x8 __attribute__((ext_vector_type(8)));
 
 // Sum of the NG producers' dh partials p[i * stride] (BPTT cell phase): for NG <= 16 all
@@ -508,13 +515,14 @@ int launch_resident(K kernel, int grid, size_t smem, hipStream_t st, const RnnAr
 
 // The kernel files' entries: each picks its kernel's instantiation for (cell, BC, the plan in a) and
 // launches it through launch_resident; hipErrorInvalidValue for a BC that is not instantiated.
-// mf: the bf16 MFMA matvec (else the fp32 VALU one).
+// mf: the bf16 MFMA matvec (else the fp32 VALU one).  hard: Keras 1's hard_sigmoid gates (fp32 LSTM only; the
+// runtime-bounds instantiations, so the BPTT's LDS is sized for bwd_dims' generic maxima).
 // RNN_EXP_MINIMAL (experiment variant libraries only, tools/variant_lib.py --minimal): only the packed
 // bf16 kernels at BC = 4 are instantiated -- the C2 / C4 training step at B = 32 -- so a variant of a
 // packed-kernel file compiles in a fraction of the full build's time; every other plan fails its launch.
-int launch_fwd(const RnnArgs& a, int cell, int BC, bool mf, int grid, size_t smem, hipStream_t st);
+int launch_fwd(const RnnArgs& a, int cell, int BC, bool mf, bool hard, int grid, size_t smem, hipStream_t st);
 int launch_fwd_pk(const RnnArgs& a, int cell, int BC, int grid, size_t smem, hipStream_t st);
-int launch_bwd(const RnnArgs& a, int cell, int BC, bool mf, int grid, size_t smem, hipStream_t st);
+int launch_bwd(const RnnArgs& a, int cell, int BC, bool mf, bool hard, int grid, size_t smem, hipStream_t st);
 int launch_bwd_pk(const RnnArgs& a, int cell, int BC, int grid, size_t smem, hipStream_t st);
 
 }  // namespace dl4ss_rnn

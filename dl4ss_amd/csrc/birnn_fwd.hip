@@ -11,8 +11,12 @@ namespace dl4ss_rnn {
 //      throughput mode): wave m owns the 16-row tile m of W_hh (bf16 A fragments in
 //      registers for all K), h staged in LDS as bf16 [batch][k] (the B operand), one
 //      MFMA chain per wave -- no partial sums at all.
-template <int CELL, int BC, int KPL_T, bool MF, int HM = HMAX>
+// HARD = true: Keras 1's LSTM cell (DL4SS_RNN_HARD_GATES): the i, f and o gates are hard_sigmoid of
+//      the same pre-activation (one FMA and a clamp, hsig of birnn_common.h) instead of the logistic
+//      function; g, c and h are unchanged.  fp32 LSTM, runtime-bounds instantiations only.
+template <int CELL, int BC, int KPL_T, bool MF, int HM = HMAX, bool HARD = false>
 __global__ __launch_bounds__(NT, 1) void rnn_fwd_kernel(RnnArgs a) {
+  static_assert(!HARD || (CELL == CELL_LSTM && !MF && KPL_T == 0), "hard gates: fp32 LSTM, runtime bounds");
   constexpr int WN = MF ? 1 : (KPL_T > 0 ? KPL_T : WMAX);  // fp32 weights per thread (compile-time)
   constexpr int NGATE = CELL == CELL_LSTM ? 4 : 3;
   constexpr int KSMAX = HM / 32;
@@ -211,10 +215,10 @@ __global__ __launch_bounds__(NT, 1) void rnn_fwd_kernel(RnnArgs a) {
         float hn = 0.0f, st[4] = {0.f, 0.f, 0.f, 0.f};
         if (cval) {
           if constexpr (CELL == CELL_LSTM) {
-            const float ig = fsig(gx[0] + hg[0]);
-            const float fg = fsig(gx[1] + hg[1]);
+            const float ig = HARD ? hsig(gx[0] + hg[0]) : fsig(gx[0] + hg[0]);
+            const float fg = HARD ? hsig(gx[1] + hg[1]) : fsig(gx[1] + hg[1]);
             const float gg = ftanh(gx[2] + hg[2]);
-            const float og = fsig(gx[3] + hg[3]);
+            const float og = HARD ? hsig(gx[3] + hg[3]) : fsig(gx[3] + hg[3]);
             cst = fg * cst + ig * gg;
             hn = og * ftanh(cst);
             st[0] = ig; st[1] = fg; st[2] = gg; st[3] = og;
@@ -248,10 +252,19 @@ __global__ __launch_bounds__(NT, 1) void rnn_fwd_kernel(RnnArgs a) {
 
 namespace {
 template <int CELL, int BC>
-int launch_fwd_t(const RnnArgs& a, bool mf, int grid, size_t smem, hipStream_t st) {
+int launch_fwd_t(const RnnArgs& a, bool mf, bool hard, int grid, size_t smem, hipStream_t st) {
 #ifdef RNN_EXP_MINIMAL
   return (int)hipErrorNotSupported;
 #else
+  if (hard) {  // Keras 1's cell: fp32 LSTM at the runtime-bounds instantiations only
+    if constexpr (CELL == CELL_LSTM) {
+      if (mf) return (int)hipErrorInvalidValue;
+      if (a.H > HMAX) return launch_resident(rnn_fwd_kernel<CELL, BC, 0, false, HMAX_L, true>, grid, smem, st, a);
+      return launch_resident(rnn_fwd_kernel<CELL, BC, 0, false, HMAX, true>, grid, smem, st, a);
+    } else {
+      return (int)hipErrorInvalidValue;
+    }
+  }
   if (a.H > HMAX) {  // forward-only large-H instantiations (the H = 600 classifier)
     if (mf)
       return launch_resident(rnn_fwd_kernel<CELL, BC, 0, true, HMAX_L>, grid, smem, st, a);
@@ -270,20 +283,20 @@ int launch_fwd_t(const RnnArgs& a, bool mf, int grid, size_t smem, hipStream_t s
 #endif
 }
 template <int CELL>
-int launch_fwd_c(const RnnArgs& a, int BC, bool mf, int grid, size_t smem, hipStream_t st) {
+int launch_fwd_c(const RnnArgs& a, int BC, bool mf, bool hard, int grid, size_t smem, hipStream_t st) {
   switch (BC) {
-    case 1: return launch_fwd_t<CELL, 1>(a, mf, grid, smem, st);
-    case 2: return launch_fwd_t<CELL, 2>(a, mf, grid, smem, st);
-    case 4: return launch_fwd_t<CELL, 4>(a, mf, grid, smem, st);
-    case 8: return launch_fwd_t<CELL, 8>(a, mf, grid, smem, st);
+    case 1: return launch_fwd_t<CELL, 1>(a, mf, hard, grid, smem, st);
+    case 2: return launch_fwd_t<CELL, 2>(a, mf, hard, grid, smem, st);
+    case 4: return launch_fwd_t<CELL, 4>(a, mf, hard, grid, smem, st);
+    case 8: return launch_fwd_t<CELL, 8>(a, mf, hard, grid, smem, st);
     default: return (int)hipErrorInvalidValue;
   }
 }
 }  // namespace
 
-int launch_fwd(const RnnArgs& a, int cell, int BC, bool mf, int grid, size_t smem, hipStream_t st) {
-  return cell == CELL_LSTM ? launch_fwd_c<CELL_LSTM>(a, BC, mf, grid, smem, st)
-                           : launch_fwd_c<CELL_GRU>(a, BC, mf, grid, smem, st);
+int launch_fwd(const RnnArgs& a, int cell, int BC, bool mf, bool hard, int grid, size_t smem, hipStream_t st) {
+  return cell == CELL_LSTM ? launch_fwd_c<CELL_LSTM>(a, BC, mf, hard, grid, smem, st)
+                           : launch_fwd_c<CELL_GRU>(a, BC, mf, hard, grid, smem, st);
 }
 
 }  // namespace dl4ss_rnn

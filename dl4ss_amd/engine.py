@@ -411,7 +411,7 @@ class SepTrainer:
             else:
                 ops.gemm(xin, w, transB=True, bias=net.cat_view("bias_ih", l), out=self.G, precision=self.precision)
             ops.birnn_fwd(net.cell, B, T, H, G=self.G, out=self.out[l], precision=self.rnn_precision,
-                          flags=WS_ZEROED if fast else 0, **kw)
+                          flags=(WS_ZEROED if fast else 0) | self.rnn_flags, **kw)
         xin, w = self._fwd_operands(net.L, x)
         if fast:  # bf16: V itself is bf16 (the EPI_TANH_BF16 epilogue); bf16s keeps it fp32
             self._gemm_fwd(xin, w, net.view("mix.Linear.bias"), self.Vb if bf16v else self.V,
@@ -754,7 +754,7 @@ class SepTrainer:
                           dOut_bcast=self.dh_bcast if (l == net.L - 1 and net.adjust) else None,
                           w_hh=net.cat_view("weight_hh", l), act=self.act[l], cs=self.cs[l] if self.cs else None,
                           hprev=self.hprev[l], dG=dG, dGh=self.dGh, ws=self.rnn_ws, ws_bytes=self.ws_bytes,
-                          status=self.status)
+                          status=self.status, flags=self.rnn_flags)
             xl = self.mag_mix.view(BT, -1) if l == 0 else self.out[l - 1].view(BT, 2 * H)
             ops.gemm(dG, xl, transA=True, out=net.cat_view("weight_ih", l, g), splitk=self._sk, beta=1.0,
                      precision=self.precision, **self._gk)

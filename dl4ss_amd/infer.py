@@ -71,15 +71,17 @@ class _BiRNNStack:
         self.ws = torch.empty((wsn + 7) // 8, dtype=torch.int64, device=device)
         self.status = torch.zeros(1, dtype=torch.int32, device=device)
 
-    def run(self, x2d, cat_view, precision, rnn_precision=None, split_w=None):
+    def run(self, x2d, cat_view, precision, rnn_precision=None, split_w=None, gates="logistic"):
         """x2d (B*T, D0) fp32 -> (B, T, 2H); cat_view(kind, l) gives the [fwd; reverse]
         parameter of layer l (``weight_ih`` / ``weight_hh`` / ``bias_ih`` / ``bias_hh``).
         ``precision``: the input-projection GEMMs -- "fp32", "bf16", or "bf16s": one bf16 LDS-DMA
         GEMM over split operands (K' = 3 K, fp32-accurate to ~2^-16; the training step's bf16s
         forward GEMMs), with ``split_w`` (a _SplitWeights) holding the weight images;
-        ``rnn_precision`` (default: the same; "bf16" for bf16s) the recurrent matvec."""
+        ``rnn_precision`` (default: the same; "bf16" for bf16s) the recurrent matvec; ``gates`` "hard": Keras 1's
+        LSTM cell (the fp32 recurrence only: ops.gate_flags refuses the rest)."""
         B, T, H = self.B, self.T, self.H
         rnn_precision = rnn_precision or ("bf16" if precision == "bf16s" else precision)
+        flags = ops.gate_flags(gates, self.cell, rnn_precision)
         x = x2d
         out = None
         for l in range(self.L):
@@ -95,7 +97,7 @@ class _BiRNNStack:
             out = self.out[l % 2]
             ops.birnn_fwd(self.cell, B, T, H, G=self.G, w_hh=cat_view("weight_hh", l), b_hh=cat_view("bias_hh", l),
                           out=out, hprev=self.hprev, act=self.act, cs=self.cs, ws=self.ws, ws_bytes=self.wsn,
-                          status=self.status, precision=rnn_precision)
+                          status=self.status, precision=rnn_precision, flags=flags)
             x = out.view(B * T, 2 * H)
         return out
 
@@ -180,11 +182,14 @@ class ClassifierForward:
 class MaskNetForward:
     """MIX_SPEECH forward on a SepNet: V (B*T, F*E) = tanh(Linear(BiRNN(X))).  ``precision``: the
     GEMMs (input projections, Linear; "fp32", "bf16" or the split-operand "bf16s");
-    ``rnn_precision`` (default: the same, "bf16" for bf16s): the recurrence."""
+    ``rnn_precision`` (default: the same, "bf16" for bf16s): the recurrence.  A net with ``gates="hard"`` (Keras 1's
+    LSTM cell) runs on the fp32 recurrence only: any other is refused here, before a device call."""
 
     def __init__(self, net, B, T, precision="fp32", rnn_precision=None):
         self.net, self.B, self.T, self.precision = net, B, T, precision
         self.rnn_precision = rnn_precision or ("bf16" if precision == "bf16s" else precision)
+        self.gates = getattr(net, "gates", "logistic")
+        ops.gate_flags(self.gates, net.cell, self.rnn_precision)
         self.stack = _BiRNNStack(net.cell, net.H, net.L, B, T, net.device)
         self.split_w = _SplitWeights(net) if precision == "bf16s" else None
         self.h = None
@@ -192,7 +197,7 @@ class MaskNetForward:
     def __call__(self, feats, out):
         B, T, net = self.B, self.T, self.net
         self.h = self.stack.run(feats.reshape(B * T, -1), net.cat_view, self.precision, self.rnn_precision,
-                                split_w=self.split_w)
+                                split_w=self.split_w, gates=self.gates)
         h2 = self.h.view(B * T, 2 * net.H)
         if self.precision == "bf16s":
             seg = pad8(2 * net.H)

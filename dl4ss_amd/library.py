@@ -22,6 +22,9 @@ conj)``                                cRM_EvalVer.py:96-99,720-728)
 ``dl4ss::mix_sources(raw, gains)``     normalise + gain + sum (predata_multiAims_dB.py:156-197)
 ``dl4ss::birnn_layer(x, w_ih, b_ih,    one bidirectional LSTM / GRU layer (EvalVer.py:282-293,
 w_hh, b_hh, cell, H, precision)``      main_run.py:263-273); returns (out, hprev, act, cs)
+``dl4ss::keras_lstm_layer(x, w_ih,     one layer of Keras 1's Bidirectional(LSTM(...)), hard_sigmoid
+b_ih, w_hh, b_hh, H)``                 gates (DL4SS_Keras/nnet.py:51-68); fp32; returns (out, hprev,
+                                       act, cs)
 ``dl4ss::linear_tanh(x, w, b, prec)``  MIX_SPEECH head tanh(Linear) (EvalVer.py:290,298-299)
 ``dl4ss::attention_dot(V, q, crm)``    ATTENTION 'dot' mask (EvalVer.py:216-226, cRM:259-271)
 ``dl4ss::attention_align(V, q, W1,     ATTENTION 'align' mask (EvalVer.py:228-239,
@@ -171,8 +174,58 @@ def _birnn_backward(ctx, dout, _dhprev, _dact, _dcs):
 birnn_layer.register_autograd(_birnn_backward, setup_context=_birnn_setup)
 
 
-def birnn(x, w_ih, b_ih, w_hh, b_hh, cell="lstm", H=300, precision="fp32"):
-    """One bidirectional layer through ``dl4ss::birnn_layer``: out (B, T, 2H) only."""
+# Keras 1's LSTM cell (hard_sigmoid i / f / o gates, ops.HARD_GATES): an op of its own, so the schemas of
+# birnn_layer / birnn_layer_bwd stay as they are.  The same tensors, LSTM and the fp32 recurrence only.
+@_op("keras_lstm_layer")
+def keras_lstm_layer(x: Tensor, w_ih: Tensor, b_ih: Tensor, w_hh: Tensor, b_hh: Tensor,
+                     H: int) -> Tuple[Tensor, Tensor, Tensor, Tensor]:
+    return ag.birnn_fwd_impl(x, w_ih, b_ih, w_hh, b_hh, "lstm", H, "fp32", gates="hard")
+
+
+@keras_lstm_layer.register_fake
+def _(x, w_ih, b_ih, w_hh, b_hh, H):
+    B, T, _ = x.shape
+    return (x.new_empty(B, T, 2 * H, **F32), x.new_empty(B, T, 2 * H, **F32), x.new_empty(B, T, 2, 4 * H, **F32),
+            x.new_empty(B, T, 2, H, **F32))
+
+
+@_op("keras_lstm_layer_bwd")
+def keras_lstm_layer_bwd(dout: Tensor, x: Tensor, w_ih: Tensor, w_hh: Tensor, hprev: Tensor, act: Tensor, cs: Tensor,
+                         H: int, need_dx: bool) -> Tuple[Tensor, Tensor, Tensor, Tensor, Tensor]:
+    dx, dw_ih, db_ih, dw_hh, db_hh = ag.birnn_bwd_impl(dout, x, w_ih, w_hh, hprev, act, cs, "lstm", H, "fp32",
+                                                       need_dx, gates="hard")
+    return (dx if dx is not None else x.new_empty(0)), dw_ih, db_ih, dw_hh, db_hh
+
+
+@keras_lstm_layer_bwd.register_fake
+def _(dout, x, w_ih, w_hh, hprev, act, cs, H, need_dx):
+    return (torch.empty_like(x, **F32) if need_dx else x.new_empty(0, **F32), torch.empty_like(w_ih, **F32),
+            x.new_empty(8 * H, **F32), torch.empty_like(w_hh, **F32), x.new_empty(8 * H, **F32))
+
+
+def _keras_lstm_setup(ctx, inputs, output):
+    x, w_ih, b_ih, w_hh, b_hh, H = inputs
+    _, hprev, act, cs = output
+    ctx.mark_non_differentiable(hprev, act, cs)
+    ctx.save_for_backward(x, w_ih, w_hh, hprev, act, cs)
+    ctx.H = H
+
+
+def _keras_lstm_backward(ctx, dout, _dhprev, _dact, _dcs):
+    x, w_ih, w_hh, hprev, act, cs = ctx.saved_tensors
+    dx, dw_ih, db_ih, dw_hh, db_hh = keras_lstm_layer_bwd(dout.contiguous(), x, w_ih, w_hh, hprev, act, cs, ctx.H,
+                                                          bool(ctx.needs_input_grad[0]))
+    return (dx if ctx.needs_input_grad[0] else None), dw_ih, db_ih, dw_hh, db_hh, None
+
+
+keras_lstm_layer.register_autograd(_keras_lstm_backward, setup_context=_keras_lstm_setup)
+
+
+def birnn(x, w_ih, b_ih, w_hh, b_hh, cell="lstm", H=300, precision="fp32", gates="logistic"):
+    """One bidirectional layer through ``dl4ss::birnn_layer``: out (B, T, 2H) only.  gates "hard": Keras 1's
+    LSTM cell through ``dl4ss::keras_lstm_layer`` (cell "lstm" and the fp32 recurrence only)."""
+    if ops.gate_flags(gates, cell, precision):
+        return torch.ops.dl4ss.keras_lstm_layer(x, w_ih, b_ih, w_hh, b_hh, H)[0]
     return torch.ops.dl4ss.birnn_layer(x, w_ih, b_ih, w_hh, b_hh, cell, H, precision)[0]
 
 
@@ -399,5 +452,6 @@ spk_memory.register_autograd(_spk_backward, setup_context=_spk_setup)
 
 
 OPS = ("stft_mag", "stft_complex", "istft", "istft_apply", "mix_sources", "birnn_layer", "birnn_layer_bwd",
+       "keras_lstm_layer", "keras_lstm_layer_bwd",
        "linear_tanh", "linear_tanh_bwd", "attention_dot", "attention_dot_bwd", "attention_align",
        "attention_align_bwd", "top_k_mask", "discriminator", "discriminator_bwd", "spk_memory", "spk_memory_bwd")

@@ -588,6 +588,24 @@ CELLS = {"lstm": _C["DL4SS_CELL_LSTM"], "gru": _C["DL4SS_CELL_GRU"]}
 WS_ZEROED = _C["DL4SS_RNN_WS_ZEROED"]  # the caller keeps the hand-off workspace zeroed
 DGH_PAD8 = _C["DL4SS_RNN_DGH_PAD8"]  # each direction's bf16 dGh columns start 16-B aligned
 DEFER_BIAS = _C["DL4SS_RNN_DEFER_BIAS"]  # bias partials stay in the workspace (dl4ss_birnn_bias_reduce)
+HARD_GATES = _C["DL4SS_RNN_HARD_GATES"]  # Keras 1's LSTM cell: hard_sigmoid i / f / o gates (fp32 LSTM only)
+GATES = ("logistic", "hard")
+
+
+def gate_flags(gates, cell="lstm", precision="fp32"):
+    """The recurrence flag of a net's ``gates`` setting: 0 for "logistic", HARD_GATES for "hard", which exists
+    for the LSTM on the fp32 recurrence only (ValueError otherwise, before any device call)."""
+    if gates not in GATES:
+        raise ValueError(f"gates {gates!r}: expected one of {GATES}")
+    if gates == "logistic":
+        return 0
+    if cell != "lstm":
+        raise ValueError(f"gates='hard' is Keras 1's LSTM cell: cell {cell!r} has no hard-gates form")
+    if PREC[precision] != 0:
+        raise ValueError("gates='hard' (Keras 1's LSTM cell) needs the fp32 recurrence: the packed bf16 recurrence "
+                         f"has no hard-gates form (the recurrence resolves to {precision!r}; use precision='fp32', "
+                         "or precision='bf16' with rnn_precision='fp32')")
+    return HARD_GATES
 
 
 def DOUT_SLABS(n):  # DL4SS_RNN_DOUT_SLABS(S): the BPTT sums dOut's S split-K slabs itself

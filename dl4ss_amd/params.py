@@ -11,6 +11,17 @@ def _ngate(cell):
     return 4 if cell == "lstm" else 3
 
 
+def check_gates(gates, cell, who):
+    """A net's ``gates`` setting: "logistic" (torch's cell) or "hard" (Keras 1's LSTM cell, whose i / f / o gates are
+    hard_sigmoid: DL4SS_RNN_HARD_GATES), the latter for cell "lstm" only.  Returns it."""
+    if gates not in ("logistic", "hard"):
+        raise ValueError(f"{who}: gates {gates!r}, expected 'logistic' or 'hard'")
+    if gates == "hard" and cell != "lstm":
+        raise ValueError(f"{who}: gates='hard' is Keras 1's LSTM cell and needs cell='lstm', got cell {cell!r} "
+                         "(Keras's GRU is a different cell from this one and is not built)")
+    return gates
+
+
 class FlatParams:
     """Parameters in one flat fp32 buffer with named views (16-B aligned) under the reference's
     ``state_dict`` key names; ``layer_prefix`` + ``{kind}_l{l}[_reverse]`` names the recurrent layers'."""
@@ -59,12 +70,15 @@ class FlatParams:
 
 
 class SepNet(FlatParams):
-    """Trainable parameters of the mask network, flat fp32 with named views."""
+    """Trainable parameters of the mask network, flat fp32 with named views.  ``gates``: "logistic" (torch's
+    LSTM / GRU) or "hard", Keras 1's LSTM cell (hard_sigmoid i / f / o gates; cell "lstm", the fp32 recurrence):
+    a setting that travels with the net -- parameter layout and initialisation are the same."""
 
     layer_prefix = "mix.layer."
 
     def __init__(self, cell="lstm", num_layers=4, hidden=300, emb=50, num_labels=101, input_fre=129, crm=False,
-                 adjust=True, device="cuda", seed=1, attention="dot"):
+                 adjust=True, device="cuda", seed=1, attention="dot", gates="logistic"):
+        self.gates = check_gates(gates, cell, "SepNet")
         if attention not in ("dot", "align"):
             raise ValueError(f"attention={attention!r}: expected 'dot' or 'align'")
         if attention == "align" and crm:

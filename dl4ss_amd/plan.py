@@ -130,6 +130,7 @@ def check_args(net, batch, k, n_samples, mode, precision, rnn_precision, loss_ch
         raise ValueError("adv_clip_norm needs an adversary")
     if (mode == "crm") != net.crm:
         raise ValueError("cRM mode needs a cRM net (query width 2E) and vice versa")
+    check_hard_gates(net, resolve_rnn_precision(precision, rnn_precision))
     align = getattr(net, "attention", "dot") == "align"
     if adversary is not None:
         T = ops.n_frames(n_samples)
@@ -169,6 +170,21 @@ RETIRED_KNOBS = ("DL4SS_DX_SPLIT", "DL4SS_DEFER_BIAS", "DL4SS_SIDE_LATE", "DL4SS
     _lib.RETIRED_ENV  # (the three the library itself read: _lib._load refuses them for every consumer)
 
 
+def resolve_rnn_precision(precision, rnn_precision=None):
+    """The recurrent matvec's precision a step resolves to (defaults to the GEMM precision; the split-operand steps
+    run the bf16 recurrence): "fp32" the exact VALU kernels, "bf16" the packed MFMA ones."""
+    if precision in ("bf16s", "bf16s2") and rnn_precision in (None, precision):
+        return "bf16"
+    return rnn_precision or precision
+
+
+def check_hard_gates(net, rnn_precision):
+    """Refuse a hard-gates net on anything but the fp32 recurrence (host check, before any device call; the
+    refusal is ops.gate_flags', which the inference paths raise too).  Returns the recurrence's flag."""
+    gates = getattr(net, "gates", "logistic")
+    return ops.gate_flags(gates, net.cell, rnn_precision) if gates != "logistic" else 0
+
+
 def step_plan(net, batch, n_samples, precision, rnn_precision=None, process_group=None):
     """Every schedule decision of a SepTrainer, derived once from its arguments, the recurrence's plan,
     the CU count and the environment knobs -- each knob is read and validated here and nowhere else.
@@ -187,7 +203,9 @@ def step_plan(net, batch, n_samples, precision, rnn_precision=None, process_grou
     p.split = precision in ("bf16s", "bf16s2")
     p.split_x2 = precision == "bf16s2"
     # recurrent matvec precision (defaults to the GEMM precision): "fp32" exact VALU, "bf16" MFMA
-    p.rnn_precision = "bf16" if (p.split and rnn_precision in (None, precision)) else (rnn_precision or precision)
+    p.rnn_precision = resolve_rnn_precision(precision, rnn_precision)
+    # the recurrence's gate form as a launch constant (ops.HARD_GATES: Keras 1's cell, fp32 recurrence only)
+    p.rnn_flags = check_hard_gates(net, p.rnn_precision)
     if p.split and p.rnn_precision != "bf16":
         raise ValueError(f"precision '{precision}' runs the bf16 recurrence (rnn_precision bf16)")
     p.fast = precision in ("bf16", "bf16s", "bf16s2") and p.rnn_precision == "bf16"

@@ -12,8 +12,9 @@ its reverse direction over len-1 .. 0, both from a zero state; the voiceprint is
 len frames / (len + eps).  The full-length recurrence kernels give exactly that when the reverse direction's
 rows are right-aligned (``dl4ss_vp_shift``): DESIGN.md section 5, "Voiceprint memory".
 
-The cell is this project's LSTM (torch gate order, logistic gates), not Keras 1's ``hard_sigmoid``.
-fp32, single GPU, eager launches.
+The cell is this project's LSTM (torch gate order); ``VoiceprintNet(gates="hard")`` makes its i / f / o gates
+Keras 1's ``hard_sigmoid`` (the ``LSTM`` default ``inner_activation`` those lines run with;
+``DL4SS_RNN_HARD_GATES``), the default ``"logistic"`` torch's.  fp32, single GPU, eager launches.
 """
 import math
 
@@ -21,21 +22,24 @@ import torch
 
 from . import _lib, ops
 from .adam import GuardedAdam
-from .params import FlatParams
+from .params import FlatParams, check_gates
 
 EPS = 2.220446049250313e-16  # np.spacing(1)
 
 
 class VoiceprintNet(FlatParams):
     """Parameters of the voiceprint BiLSTM, flat fp32 under ``spk.layer.{kind}_l{l}[_reverse]``; ``grad`` is the
-    flat gradient of the same layout (VoiceprintEncoder.backward writes it)."""
+    flat gradient of the same layout (VoiceprintEncoder.backward writes it).  ``gates``: "logistic" or "hard"
+    (Keras 1's LSTM cell), independent of the mask net's; layout and initialisation are the same."""
 
     layer_prefix = "spk.layer."
 
-    def __init__(self, input_fre=129, emb=50, hidden=None, num_layers=2, cell="lstm", device="cuda", seed=1):
+    def __init__(self, input_fre=129, emb=50, hidden=None, num_layers=2, cell="lstm", device="cuda", seed=1,
+                 gates="logistic"):
         hidden = emb // 2 if hidden is None else hidden
         if cell != "lstm":
             raise ValueError(f"VoiceprintNet: cell {cell!r}, the voiceprint encoder is a BiLSTM")
+        self.gates = check_gates(gates, cell, "VoiceprintNet")
         if 2 * hidden != emb:
             raise ValueError(f"VoiceprintNet: 2 * hidden ({hidden}) must equal emb ({emb})")
         if num_layers < 1:
@@ -107,6 +111,7 @@ class VoiceprintEncoder:
                                       or wgrad_split < 1):
             raise ValueError(f"VoiceprintEncoder: wgrad_split {wgrad_split!r}, expected an int >= 1 or 'auto'")
         self.net, self.n, self.T, self.wgrad_split = vnet, int(n), int(T), wgrad_split
+        self.rnn_flags = ops.gate_flags(getattr(vnet, "gates", "logistic"))  # the fp32 recurrence: either form
         H, L, F, dev = vnet.H, vnet.L, vnet.F, vnet.device
         f32 = dict(device=dev, dtype=torch.float32)
         i32 = dict(device=dev, dtype=torch.int32)
@@ -152,7 +157,7 @@ class VoiceprintEncoder:
             ops.vp_shift(self.Gc, self.G, self.len, 4 * H, 8 * H, +1, other=2)
             ops.birnn_fwd("lstm", n, T, H, G=self.G, w_hh=net.cat_view("weight_hh", l), b_hh=net.cat_view("bias_hh", l),
                           out=self.out[l], hprev=self.hprev[l], act=self.act[l], cs=self.cs[l], ws=self.rnn_ws,
-                          ws_bytes=self.ws_bytes, status=self.status)
+                          ws_bytes=self.ws_bytes, status=self.status, flags=self.rnn_flags)
             if l + 1 < net.L:  # the reverse half back to the compact frame, both halves zero behind len
                 ops.vp_shift(self.out[l], self.xin[l + 1], self.len, H, 2 * H, -1, other=1)
                 x = self.xin[l + 1].view(n * T, 2 * H)
@@ -168,7 +173,7 @@ class VoiceprintEncoder:
         for l in range(net.L - 1, -1, -1):
             ops.birnn_bwd("lstm", n, T, H, dOut=self.dH, w_hh=net.cat_view("weight_hh", l), act=self.act[l],
                           cs=self.cs[l], hprev=self.hprev[l], dG=self.G, ws=self.rnn_ws, ws_bytes=self.ws_bytes,
-                          status=self.status)
+                          status=self.status, flags=self.rnn_flags)
             # dG is exactly zero on the padded rows: the bias and W_hh gradients are taken in the recurrence's frame
             db = net.cat_view("bias_ih", l, g)
             ops.vp_colsum(G2, db, self.cs_part)

@@ -196,6 +196,22 @@ enum { DL4SS_CELL_LSTM = 0, DL4SS_CELL_GRU = 1 };
  * workspaces and bias gradient pointers as host arrays) into db_ih / db_hh in ONE launch, in the
  * same fixed row order (bitwise the per-launch reduce). */
 #define DL4SS_RNN_DEFER_BIAS 0x400
+/* precision flag of dl4ss_birnn_fwd / _fwd_ex / _fwd_mean / dl4ss_birnn_bwd / _bwd_ex: Keras 1's LSTM cell
+ * (Bidirectional(LSTM(...)) of Cocktail/software/DL4SS_Keras/nnet.py:51-68 with Keras 1's default
+ * inner_activation='hard_sigmoid').  With z = G + W_hh h + b_hh exactly as the logistic cell forms it,
+ *   i, f, o = hs(z),  hs(z) = min(max(fma(0.2f, z, 0.5f), 0), 1)     (Theano's hard_sigmoid)
+ *   g = tanh(z_g),  c = f c + i g,  h = o tanh(c)                      (unchanged)
+ * and act holds the clipped gate values in the logistic cell's layout.  The BPTT takes the gate derivative
+ * from the saved activation s as the logistic form takes s (1 - s): hs'(s) = 0.2f where 0 < s < 1, else 0;
+ *   dG_i = dc g hs'(i),  dG_f = dc c_prev hs'(f),  dG_o = dh tanh(c) hs'(o);  dG_g, dc, dc_next unchanged.
+ * A flag, not a third cell id: the gate count, the layouts, the plan (dl4ss_birnn_plan_info) and the
+ * workspace size are DL4SS_CELL_LSTM's.  Accepted only with cell == DL4SS_CELL_LSTM and base precision 0 (the
+ * generic fp32 kernels, any H <= 640); every other combination returns hipErrorInvalidValue before any
+ * launch or device call: DL4SS_CELL_GRU, precision 1, out_bf16 / hprev_bf16 / h_mean, dG_bf16 / dGh_bf16 and
+ * DL4SS_RNN_DOUT_SLABS.  (Keras's GRU is not this flag on DL4SS_CELL_GRU: besides hard_sigmoid it applies the
+ * reset gate to h before the recurrent product, n = tanh(W x + U (r h)), where torch's -- this library's --
+ * applies it after, n = tanh(W x + r (U h + b)): a different cell, not built.) */
+#define DL4SS_RNN_HARD_GATES 0x800
 /* precision field of dl4ss_birnn_bwd_ex (bits 12-13: S - 1): dOut is not one (B, T, 2H) array but the S
  * (2..4) fp32 split-K slabs dl4ss_gemm_bf16_gl leaves with DL4SS_EPI_SPLIT_SLABS, slab z at dOut + z B T 2H;
  * the BPTT sums them per element in slab order from zero (((0 + s0) + s1) + ...), bitwise the combine
