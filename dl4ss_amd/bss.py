@@ -20,6 +20,7 @@ The correlations (the only O(N L) work: 4.2 GMAC fp64 for 32 two-speaker mixture
 and the Gram assembly are HIP kernels (``bss.hip``); the dense SPD solves are batched fp64
 Cholesky factorisations through torch.linalg (rocSOLVER) on the same stream.
 """
+import ctypes
 import itertools
 
 import numpy as np
@@ -77,6 +78,50 @@ def bss_eval_matrices(refs, ests, flen=FLEN):
     sir = _criteria_db(q_j, qa - q_j)
     sar = _criteria_db(qa.expand_as(q_j), E - qa)
     return sdr, sir, sar
+
+
+def bss_eval_gain(srcs, ests, index, lengths=None):
+    """BSS Eval 2.0's gain decomposition (``bss_decomp_gain`` + ``bss_crit``; include/dl4ss_eval.h), batched:
+    srcs (M, J, N), ests (M, Ke, N) float32 on the device, ``index`` Ke ints (estimate e estimates source
+    index[e]), ``lengths`` (M) int32 on the device (None: N) -- only the first lengths[m] samples of utterance m
+    exist.  Returns ((sdr, sir, sar), singular): three (M, Ke) float64 device tensors and the int32 device count
+    (1 element) of (utterance, estimate) pairs whose Gram matrix was singular (their criteria are NaN).  Nothing
+    syncs with the host."""
+    if not (srcs.is_cuda and ests.is_cuda):
+        raise RuntimeError("bss_eval_gain runs on the GPU (no CPU fallback)")
+    if srcs.dim() != 3 or ests.dim() != 3 or srcs.shape[0] != ests.shape[0] or srcs.shape[2] != ests.shape[2]:
+        raise ValueError(f"bss_eval_gain: srcs {tuple(srcs.shape)} and ests {tuple(ests.shape)} must be (M, J, N) "
+                         "and (M, Ke, N)")
+    if srcs.dtype != torch.float32 or ests.dtype != torch.float32:
+        raise ValueError("bss_eval_gain: float32 signals")
+    M, J, N = srcs.shape
+    Ke = ests.shape[1]
+    index = [int(i) for i in index]
+    if not (1 <= J <= 4 and 1 <= Ke <= 4) or len(index) != Ke or any(not 0 <= i < J for i in index) or N < 1:
+        raise ValueError(f"bss_eval_gain: J = {J}, Ke = {Ke} must be 1..4, N >= 1, and index {index} Ke entries "
+                         "in [0, J)")
+    if lengths is not None and (lengths.dtype != torch.int32 or tuple(lengths.shape) != (M,) or not lengths.is_cuda):
+        raise ValueError("bss_eval_gain: lengths must be (M) int32 on the device")
+    dev = srcs.device
+    ws_bytes = _lib.query("dl4ss_bss_gain_ws_bytes", M, N)
+    ws = torch.empty(max(ws_bytes, 8) // 8, dtype=torch.float64, device=dev)
+    crit = torch.empty(M, Ke, 3, dtype=torch.float64, device=dev)
+    singular = torch.empty(1, dtype=torch.int32, device=dev)
+    _lib.call("dl4ss_bss_gain", src=_lib.ptr(srcs), est=_lib.ptr(ests), index=(ctypes.c_int * Ke)(*index),
+              n_eff=_lib.ptr(lengths), M=M, J=J, Ke=Ke, N=N, ws=_lib.ptr(ws), ws_bytes=ws_bytes,
+              crit=_lib.ptr(crit), singular=_lib.ptr(singular), stream=_lib.stream_ptr())
+    return (crit[..., 0], crit[..., 1], crit[..., 2]), singular
+
+
+def bss_eval_target(target, noise, pred, mix, lengths=None):
+    """``BSS_EVAL.m`` of the Keras trees (DL4SS_Keras/predict.py:259-282), batched: target, noise, pred, mix (M, N)
+    float32 on the device.  SDR / SIR / SAR: the gain decomposition of ``pred`` on [noise; target] with the target
+    as the source it estimates; NSDR = SDR - SDR(mix decomposed on [target] alone).  Returns a dict of (M) float64
+    device tensors ``SDR, SIR, SAR, NSDR`` and ``singular`` (the int32 device count over both decompositions)."""
+    srcs = torch.stack([noise, target], 1).contiguous()
+    (sdr, sir, sar), s1 = bss_eval_gain(srcs, pred[:, None].contiguous(), [1], lengths)
+    (sdr_mix, _, _), s2 = bss_eval_gain(target[:, None].contiguous(), mix[:, None].contiguous(), [0], lengths)
+    return dict(SDR=sdr[:, 0], SIR=sir[:, 0], SAR=sar[:, 0], NSDR=sdr[:, 0] - sdr_mix[:, 0], singular=s1 + s2)
 
 
 def bss_eval_sources(refs, ests, flen=FLEN):

@@ -261,3 +261,44 @@ def export_keras_lstm(net, layer, direction):
         out[f"U_{g}"] = p["weight_hh"][rows].detach().cpu().t().contiguous()
         out[f"b_{g}"] = p["bias_ih"][rows].detach().cpu().clone()
     return out
+
+
+# --------------------------------------------------------------------------- in-memory weight snapshots
+def _weight_tensors(obj):
+    """(owner to notify, tensor) of everything in ``obj`` that Keras's save_weights would cover: a net's or an
+    encoder's flat parameter buffer, a SpeakerMemory's rows (a layer weight there), or those of a trainer's net,
+    query encoder and memory."""
+    if hasattr(obj, "mem") and isinstance(obj.mem, torch.Tensor):  # SpeakerMemory
+        return [(None, obj.mem)]
+    if hasattr(obj, "flat") and isinstance(obj.flat, torch.Tensor):  # SepNet, VoiceprintNet, ImageQueryNet, ...
+        return [(obj, obj.flat)]
+    if hasattr(obj, "net") and hasattr(obj, "opt"):  # a trainer: its net, its query encoder, its memory
+        out = [(obj, obj.net.flat)]
+        for name in ("vnet", "inet"):
+            sub = getattr(obj, name, None)
+            if sub is not None:
+                out.append((sub, sub.flat))
+        if getattr(obj, "memory", None) is not None:
+            out.append((None, obj.memory.mem))
+        return out
+    raise TypeError(f"snapshot_weights: {type(obj).__name__} has neither flat parameters nor memory rows")
+
+
+def snapshot_weights(*objs):
+    """Copies, on the tensors' own device, of the flat parameter buffers of the given nets / encoders / trainers and
+    of ``SpeakerMemory.mem`` -- what the Keras trees' ``save_weights`` covers at a new lowest validation loss
+    (nnet.py:160-165).  Optimizer state is not part of it.  Give the result to ``restore_weights``."""
+    snap = []
+    for obj in objs:
+        for owner, t in _weight_tensors(obj):
+            snap.append((owner, t, t.detach().clone()))
+    return snap
+
+
+def restore_weights(snap):
+    """Copy a ``snapshot_weights`` result back into the tensors it was taken from (nnet.py:166-169) and call
+    ``params_changed()`` on every owner that has it (a trainer re-derives its bf16 weight copies)."""
+    for owner, t, saved in snap:
+        t.copy_(saved)
+        if owner is not None and hasattr(owner, "params_changed"):
+            owner.params_changed()

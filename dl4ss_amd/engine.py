@@ -157,6 +157,7 @@ class SepTrainer:
             self.part_att = torch.empty(_lib.query("dl4ss_attn_align_part_floats", B, K, self.nblk), **f32)
         self.perm = torch.empty(B, K, device=dev, dtype=torch.int32)
         self.loss = torch.zeros(3, **f32)
+        self.eval_out = torch.zeros(3, **f32)  # eval_loss()'s result: the step's loss stays the last step's
         ws = _lib.query("dl4ss_birnn_workspace_bytes", CELLS[net.cell], B, H)
         if ws < 0:
             raise RuntimeError("unsupported BiRNN configuration")
@@ -916,6 +917,32 @@ class SepTrainer:
             self.allreduce()
         self.optimizer_step()
         return loss
+
+    def eval_loss(self, raw, gains, spk_idx, lengths=None):
+        """The trainer's own separation loss of one batch, forward only (a validation loss: what
+        DL4SS_Keras/nnet.py:149-153 takes after every epoch): features(), forward(), the attention COST pass,
+        dl4ss_pit_select in PIT mode and dl4ss_loss_finalize without dq.  Returns ``eval_out`` (device float[3]
+        {total, MSE term, weighted sum-to-one term}, not synced; the next call overwrites it).  No parameter,
+        gradient, optimizer moment, step count, status counter, memory row or parameter generation changes, and
+        ``loss`` keeps the last step's; the step's scratch buffers are overwritten, as the next step overwrites them.
+        An adversary is ignored: only the separation loss is reported.  Eager launches, also on a trainer that
+        holds a captured graph.  A voiceprint= / image_query= trainer validates the target alone:
+        targeteval.TargetEvaluator.eval_loss."""
+        if self.vp is not None or self.vnet is not None or self.inet is not None:
+            raise ValueError("eval_loss(): a voiceprint= / image_query= trainer is validated on the target alone, by "
+                             "targeteval.TargetEvaluator.eval_loss")
+        self.spk.copy_(spk_idx)
+        self.features(raw, gains, lengths)
+        self.forward()
+        self.attn(0)
+        st, perm = _lib.stream_ptr(), None
+        if self.mode == "pit":
+            _lib.call("dl4ss_pit_select", _lib.ptr(self.part_loss), self.B, self.K, self.nblk, _lib.ptr(self.perm), st)
+            perm = self.perm
+        _lib.call("dl4ss_loss_finalize", part_loss=_lib.ptr(self.part_loss), B=self.B, K=self.K, nblk=self.nblk,
+                  perm=_lib.ptr(perm), s1=self.s1, s2=self.s2, loss_out=_lib.ptr(self.eval_out), part_dq=None,
+                  qw=self.net.W, dq=None, stream=st)
+        return self.eval_out
 
     # ------------------------------------------------------------------ HIP graph
     def _graph_body(self):

@@ -348,9 +348,10 @@ class EnrolledExtractor:
         self.masks = torch.empty(B, K, T, net.F, **f32)
         self._enc = {}
 
-    def enrol(self, feats, rule="nonzero", thr=None, lengths=None):
+    def enrol(self, feats, rule="nonzero", thr=None, lengths=None, check=True):
         """feats (n, T', F) clean features -> (n, E) unit voiceprints u = v / |v| (a new tensor): what a zero
-        memory row would return for the speaker."""
+        memory row would return for the speaker.  ``check=False`` leaves out the encoder's status check, which
+        synchronises with the host (targeteval.TargetEvaluator checks once, in its own check())."""
         from .voiceprint import VoiceprintEncoder, unit
 
         if self.by_image:  # feats: images (n, h, w); the other arguments belong to the frame mask
@@ -367,7 +368,8 @@ class EnrolledExtractor:
         if enc is None:
             enc = self._enc[(n, Te)] = VoiceprintEncoder(self.vnet, n, Te)
         u = unit(enc.forward(feats.contiguous(), rule, thr, lengths))
-        enc.check()
+        if check:
+            enc.check()
         return u
 
     def run(self, feats, queries):

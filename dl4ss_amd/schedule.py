@@ -48,3 +48,31 @@ def classifier(lr=1e-5):
 def crm_evalver(lr=2e-4):
     """cRM_EvalVer.py:627 (disabled in the reference)."""
     return LRHalving(lr, every=50, floor=5e-6, enabled=False)
+
+
+class EarlyStopping:
+    """The early stopping of the Keras trees (``Cocktail/software/DL4SS_Keras/nnet.py:159-172``), host logic only.
+
+    After every epoch's validation loss, ``update(epoch, dev_loss)`` says whether to snapshot the weights (the
+    reference's ``save_weights``): from epoch ``start`` (``START_EALY_STOP``) on, when the loss is below the lowest
+    seen so far.  Epochs before ``start`` neither snapshot nor stop.  ``stop`` is then set by the reference's two
+    conditions -- ``patience`` (10) epochs since the best one, or the last epoch ``max_epoch - 1`` -- and
+    ``best_epoch`` names the snapshot to restore (``start`` itself until one improved: the reference would load a
+    file it never wrote).  A NaN loss never counts as an improvement (``nan < x`` is false)."""
+
+    def __init__(self, start, patience=10, max_epoch=None):
+        self.start, self.patience, self.max_epoch = int(start), int(patience), max_epoch
+        self.best_loss = float("inf")
+        self.best_epoch = self.start
+        self.stop = False
+
+    def update(self, epoch, dev_loss):
+        snapshot = False
+        if epoch >= self.start:
+            if dev_loss < self.best_loss:
+                self.best_loss, self.best_epoch = float(dev_loss), epoch
+                snapshot = True
+            if epoch - self.best_epoch >= self.patience or \
+                    (self.max_epoch is not None and epoch == self.max_epoch - 1):
+                self.stop = True
+        return snapshot
