@@ -1,7 +1,7 @@
 """ctypes binding of ``libdl4ss_hip.so``, derived from the C ABI's one declaration, ``include/dl4ss_hip.h``
 (and ``include/dl4ss_imgq.h``, the image-query encoder's entry points, ``include/dl4ss_optim.h``, Nadam and
-Keras's clipnorm, and ``include/dl4ss_eval.h``, the target-speaker evaluation, parsed the same way into ``IMGQ_*``,
-``OPTIM_*`` and ``EVAL_*`` tables).
+Keras's clipnorm, ``include/dl4ss_eval.h``, the target-speaker evaluation, and ``include/dl4ss_align.h``, ATTENTION 'align' on the
+bf16 steps, parsed the same way into ``IMGQ_*``, ``OPTIM_*``, ``EVAL_*`` and ``ALIGN_*`` tables).
 
 The header is parsed once at import: every prototype gives the entry point's ``argtypes`` (``SIGNATURES``), its
 ``restype`` (``RESTYPES``) and its parameter names (``PARAMS``); every enum constant and ``#define DL4SS_* <integer>``
@@ -30,6 +30,7 @@ HEADER = os.path.join(os.path.dirname(_HERE), "include", "dl4ss_hip.h")
 IMGQ_HEADER = os.path.join(os.path.dirname(_HERE), "include", "dl4ss_imgq.h")  # the image-query encoder's entry points
 OPTIM_HEADER = os.path.join(os.path.dirname(_HERE), "include", "dl4ss_optim.h")  # Nadam, Keras's clipnorm
 EVAL_HEADER = os.path.join(os.path.dirname(_HERE), "include", "dl4ss_eval.h")  # BSS Eval 2.0 gains, the eval mixture
+ALIGN_HEADER = os.path.join(os.path.dirname(_HERE), "include", "dl4ss_align.h")  # 'align' attention, bf16 V / dPre
 
 P = ctypes.c_void_p
 I = ctypes.c_int
@@ -104,7 +105,12 @@ with open(EVAL_HEADER) as _f:
 _EARLIER = set(SIGNATURES) | set(IMGQ_SIGNATURES) | set(OPTIM_SIGNATURES)
 if set(EVAL_SIGNATURES) & _EARLIER:
     raise ValueError(f"dl4ss_eval.h declares again: {sorted(set(EVAL_SIGNATURES) & _EARLIER)}")
-_ALL_PARAMS = {**PARAMS, **IMGQ_PARAMS, **OPTIM_PARAMS, **EVAL_PARAMS}
+# the fifth
+with open(ALIGN_HEADER) as _f:
+    ALIGN_SIGNATURES, ALIGN_RESTYPES, ALIGN_PARAMS, ALIGN_CONSTANTS = parse_header(_f.read(), "dl4ss_align.h")
+if set(ALIGN_SIGNATURES) & (_EARLIER | set(EVAL_SIGNATURES)):
+    raise ValueError(f"dl4ss_align.h declares again: {sorted(set(ALIGN_SIGNATURES) & (_EARLIER | set(EVAL_SIGNATURES)))}")
+_ALL_PARAMS = {**PARAMS, **IMGQ_PARAMS, **OPTIM_PARAMS, **EVAL_PARAMS, **ALIGN_PARAMS}
 # keyword -> slot of every entry point (a header name that is a Python keyword takes a trailing underscore)
 _SLOTS = {name: {p + "_" if keyword.iskeyword(p) else p: i for i, p in enumerate(ps)}
           for name, ps in _ALL_PARAMS.items()}
@@ -130,12 +136,12 @@ def _load():
         fn = getattr(lib, name)
         fn.argtypes = argtypes
         fn.restype = RESTYPES[name]
-    # the second, third and fourth headers' entry points.  A library without them still loads: the binding tests stand a
+    # the second to fifth headers' entry points.  A library without them still loads: the binding tests stand a
     # stub with the first header's names alone in for the library, and DL4SS_LIB may name a build from before
-    # imgq.hip, optim.hip or targeteval.hip.  Calling one that is missing fails in ctypes' own lookup, with the symbol's name:
+    # imgq.hip, optim.hip, targeteval.hip or the bf16 'align' forms.  Calling one that is missing fails in ctypes' own lookup, with the symbol's name:
     # there is no other path
     for sigs, restypes in ((IMGQ_SIGNATURES, IMGQ_RESTYPES), (OPTIM_SIGNATURES, OPTIM_RESTYPES),
-                           (EVAL_SIGNATURES, EVAL_RESTYPES)):
+                           (EVAL_SIGNATURES, EVAL_RESTYPES), (ALIGN_SIGNATURES, ALIGN_RESTYPES)):
         for name, argtypes in sigs.items():
             fn = getattr(lib, name, None)
             if fn is not None:
@@ -169,6 +175,10 @@ def eval_exported_symbols():
     return list(EVAL_SIGNATURES)
 
 
+def align_exported_symbols():
+    return list(ALIGN_SIGNATURES)
+
+
 def stream_ptr(stream=None):
     s = stream if stream is not None else torch.cuda.current_stream()
     return ctypes.c_void_p(s.cuda_stream)
@@ -193,7 +203,7 @@ def bind(name, args, kw):
     slots = _SLOTS.get(name)
     if slots is None:
         raise TypeError(f"{name} is not declared in include/dl4ss_hip.h, include/dl4ss_imgq.h, "
-                        "include/dl4ss_optim.h or include/dl4ss_eval.h")
+                        "include/dl4ss_optim.h, include/dl4ss_eval.h or include/dl4ss_align.h")
     n, given = len(slots), len(args) + len(kw)
     if len(args) > n:
         raise TypeError(f"{name} takes {n} arguments (the last is {_ALL_PARAMS[name][-1]!r}), {given} given")

@@ -7,7 +7,8 @@ shared library next to this file.  The library exports the C ABI declared in
 ``csrc/common.h``), so a definition that disagrees with its prototype fails to
 compile; ``include/dl4ss_imgq.h`` declares the image-query encoder's entry points
 and ``csrc/imgq.hip`` includes it in the same way, as ``csrc/optim.hip`` does ``include/dl4ss_optim.h`` (Nadam and
-Keras's clipnorm) and ``csrc/targeteval.hip`` ``include/dl4ss_eval.h`` (the target-speaker evaluation).  Objects are rebuilt only when a source or header -- the public one
+Keras's clipnorm) and ``csrc/targeteval.hip`` ``include/dl4ss_eval.h`` (the target-speaker evaluation) and ``csrc/attn_align.hip``
+``include/dl4ss_align.h`` ('align' attention on the bf16 steps).  Objects are rebuilt only when a source or header -- the public one
 included -- is newer than the object.
 """
 import concurrent.futures as cf
@@ -23,6 +24,7 @@ HEADER = os.path.join(os.path.dirname(HERE), "include", "dl4ss_hip.h")  # (commo
 IMGQ_HEADER = os.path.join(os.path.dirname(HERE), "include", "dl4ss_imgq.h")  # (imgq.hip includes it the same way)
 OPTIM_HEADER = os.path.join(os.path.dirname(HERE), "include", "dl4ss_optim.h")  # (optim.hip likewise)
 EVAL_HEADER = os.path.join(os.path.dirname(HERE), "include", "dl4ss_eval.h")  # (targeteval.hip likewise)
+ALIGN_HEADER = os.path.join(os.path.dirname(HERE), "include", "dl4ss_align.h")  # (attn_align.hip likewise)
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 ARCH = "gfx950"
 FLAGS = ["-O3", "-fPIC", "-std=c++17", f"--offload-arch={ARCH}", "-munsafe-fp-atomics",
@@ -53,7 +55,7 @@ def build(verbose=False, jobs=None):
     os.makedirs(OBJ, exist_ok=True)
     srcs = sorted(f for f in os.listdir(CSRC) if f.endswith(".hip"))
     headers = [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".h")]
-    headers += [HEADER, IMGQ_HEADER, OPTIM_HEADER, EVAL_HEADER]
+    headers += [HEADER, IMGQ_HEADER, OPTIM_HEADER, EVAL_HEADER, ALIGN_HEADER]
     objs, todo = [], []
     for f in srcs:
         src = os.path.join(CSRC, f)

@@ -31,7 +31,11 @@
 // All sums run in a fixed order; per-block partials (dW1 for even / odd rows, dp, dw3) are summed
 // by dl4ss_attn_align_finalize in block order: no float atomics, bitwise reproducible.
 // The two LDS tiles are 100 KB: one workgroup (one wave per SIMD) per CU.
+// The bf16 step's forms (align_io_kernel, dl4ss_mask_attn_align_loss_ex) change the two ends only: step 1 reads
+// bf16 V and widens it into the same fp32 sv, step 6 rounds dPre to bf16 on its way out, into rows of the GEMMs'
+// pitch.  The kernel text is attn_align_body.h, included into both kernel definitions.
 #include "common.h"
+#include "../../include/dl4ss_align.h"
 
 namespace {
 
@@ -73,297 +77,29 @@ __device__ __forceinline__ float tanh_e(float x) {
   return 1.f - 2.f * __builtin_amdgcn_rcpf(e + 1.f);
 }
 
+// The bf16 step's I/O forms of the fused passes (align_io_kernel): V read as bf16, dPre written as bf16 rows
+struct AlignIO {
+  const unsigned short* Vb;  // VB: (B, R, E) bf16, 4-B aligned (the Linear's EPI_TANH_BF16 output)
+  unsigned short* dPreB;     // DB: (B T, ldpb) bf16, 4-B aligned; row (t, f) of b at (b T + t) ldpb + f E
+  long long ldpb;            // even, >= F E
+  int T, F;                  // R = T F
+};
+
 template <int K, int MODE>
 __global__ __launch_bounds__(NT) void align_kernel(AlignArgs a, const float* __restrict__ W1,
                                                     const float* __restrict__ W2, const float* __restrict__ w3) {
-  constexpr bool FUSED = MODE == COST || MODE == GRAD;
-  constexpr bool BWD = MODE == GRAD || MODE == MBWD;
-  static_assert(FUSED || K == 1, "the module-level kernels take one query per row of V");
-  __shared__ __attribute__((aligned(16))) float sv[TILE * E];
-  __shared__ __attribute__((aligned(16))) float su[TILE * E];
-  __shared__ float sp[K * E];
-  __shared__ float sw3[E];
-  __shared__ float sred[NT / 64][K * K + 1];
-  __shared__ float scol[BWD ? NCH * (K + 1) * E : 1];
+  constexpr bool VB = false, DB = false;
+  constexpr AlignIO io{};
+#include "attn_align_body.h"
+}
 
-  const int b = blockIdx.y;
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  // p_k = W2 q_k, the same chain in every block of the utterance
-  if (tid < K * E) {
-    const int k = tid / E, aa = tid - k * E;
-    const float* qk = a.q + (long long)b * a.qs + k * E;
-    float acc = 0.f;
-    for (int e = 0; e < E; ++e) acc = fmaf(W2[aa * E + e], qk[e], acc);
-    sp[tid] = acc;
-  } else if (tid < K * E + E) {
-    sw3[tid - K * E] = w3[tid - K * E];
-  }
-
-  const int per = (a.R + a.nblk - 1) / a.nblk;
-  const int rbeg = blockIdx.x * per;
-  const int rend = min(a.R, rbeg + per);
-
-  int pm[K];
-#pragma unroll
-  for (int k = 0; k < K; ++k) pm[k] = (FUSED && a.perm) ? a.perm[b * K + k] : k;
-  float cost[K * K + 1];
-#pragma unroll
-  for (int i = 0; i < K * K + 1; ++i) cost[i] = 0.f;
-  // backward accumulators, kept over the block's tiles: the lane's 5 x 5 block of dW1 (lanes < 200)
-  // and its column sums (lanes < 250): dp_k (K) and dw3
-  float w1a[5][5];
-  float col[K + 1];
-#pragma unroll
-  for (int i = 0; i < 5; ++i)
-#pragma unroll
-    for (int j = 0; j < 5; ++j) w1a[i][j] = 0.f;
-#pragma unroll
-  for (int j = 0; j < K + 1; ++j) col[j] = 0.f;
-  const int wg = tid / 100, wid = tid - wg * 100;  // dW1: row parity, block id
-  const int wa0 = (wid / 10) * 5, we0 = (wid % 10) * 5;
-  const int ca = tid % E, cc = tid / E;            // column sums: column, row class
-
-  const float* Vb = a.V + (long long)b * a.R * E;
-  float* Db = (BWD && a.dPre) ? a.dPre + (long long)b * a.R * E : nullptr;
-
-  for (int r0 = rbeg; r0 < rend; r0 += TILE) {
-    const int nr = min(TILE, rend - r0);
-    __syncthreads();  // the previous tile is out of sv / su (and sp, sw3 are visible on the first pass)
-    {
-      const float* src = Vb + (long long)r0 * E;
-      const int n = nr * E;
-      if (((uintptr_t)src & 15) == 0) {
-        const int n4 = n >> 2;
-        for (int i = tid; i < n4; i += NT) reinterpret_cast<float4*>(sv)[i] = reinterpret_cast<const float4*>(src)[i];
-        for (int i = (n4 << 2) + tid; i < n; i += NT) sv[i] = src[i];
-      } else {
-        for (int i = tid; i < n; i += NT) sv[i] = src[i];
-      }
-    }
-    __syncthreads();
-    const int r = tid;
-    const bool live = r < nr;
-    const int row = r0 + r;
-    float* vrow = sv + r * E;
-    float* urow = su + r * E;
-    float s[K][E];
-    float dl[K];
-    if (live) {
-      // ---- U = W1 v (W1 rows are wave-uniform: scalar operands)
-      {
-        float v[E];
-#pragma unroll
-        for (int e = 0; e < E; e += 2) {
-          const float2 vv = *reinterpret_cast<const float2*>(vrow + e);
-          v[e] = vv.x;
-          v[e + 1] = vv.y;
-        }
-#pragma unroll 2
-        for (int aa = 0; aa < E; ++aa) {
-          const float* w = W1 + aa * E;
-          float a0 = 0.f, a1 = 0.f;
-#pragma unroll
-          for (int e = 0; e < E; e += 2) {
-            a0 = fmaf(w[e], v[e], a0);
-            a1 = fmaf(w[e + 1], v[e + 1], a1);
-          }
-          urow[aa] = a0 + a1;
-        }
-      }
-      // ---- s_k = tanh(U + p_k), logits
-      float lg[K];
-#pragma unroll
-      for (int k = 0; k < K; ++k) lg[k] = 0.f;
-#pragma unroll
-      for (int aa = 0; aa < E; aa += 2) {
-        const float2 uu = *reinterpret_cast<const float2*>(urow + aa);
-#pragma unroll
-        for (int k = 0; k < K; ++k) {
-          s[k][aa] = tanh_e(uu.x + sp[k * E + aa]);
-          s[k][aa + 1] = tanh_e(uu.y + sp[k * E + aa + 1]);
-          lg[k] = fmaf(sw3[aa], s[k][aa], lg[k]);
-          lg[k] = fmaf(sw3[aa + 1], s[k][aa + 1], lg[k]);
-        }
-      }
-      float m[K];
-#pragma unroll
-      for (int k = 0; k < K; ++k) m[k] = sigmoidf_(lg[k]);
-      if constexpr (FUSED) {
-        // the loss terms of dl4ss_mask_attn_loss (EvalVer.py:641,659-666)
-        const float x = a.X[(long long)b * a.xs + row];
-        float y[K], msum = 0.f;
-#pragma unroll
-        for (int k = 0; k < K; ++k) {
-          msum += m[k];
-          y[k] = a.Y[(long long)b * a.ys + (long long)k * a.yks + row];
-        }
-#pragma unroll
-        for (int k = 0; k < K; ++k)
-#pragma unroll
-          for (int j = 0; j < K; ++j) {
-            const float dd = m[k] * x - y[j];
-            cost[k * K + j] = fmaf(dd, dd, cost[k * K + j]);
-          }
-        const float ds = msum - 1.0f;
-        cost[K * K] = fmaf(ds, ds, cost[K * K]);
-        if (a.mask_out || a.pred_out) {
-#pragma unroll
-          for (int k = 0; k < K; ++k) {
-            const long long o = (long long)b * a.ms + (long long)k * a.R + row;
-            if (a.mask_out) a.mask_out[o] = m[k];
-            if (a.pred_out) a.pred_out[o] = m[k] * x;
-          }
-        }
-        if constexpr (MODE == GRAD) {
-#pragma unroll
-          for (int k = 0; k < K; ++k) {
-            float yp = y[0];
-#pragma unroll
-            for (int j = 1; j < K; ++j) yp = pm[k] == j ? y[j] : yp;
-            const float dm = 2.f * a.s1 * (m[k] * x - yp) * x + 2.f * a.s2 * ds;
-            dl[k] = dm * m[k] * (1.f - m[k]);
-          }
-        }
-      } else if constexpr (MODE == MFWD) {
-        a.mask_out[(long long)b * a.ms + row] = m[0];
-      } else {
-        dl[0] = a.dmask[(long long)b * a.R + row] * m[0] * (1.f - m[0]);
-      }
-    }
-    if constexpr (BWD) {
-      // ---- column sums over the tile's rows: dp_k = sum_r dS_k (j < K), dw3 = sum_r sum_k dl_k s_k (j = K).
-      // Round j: every live lane puts its row's values into su, lane (column ca, class cc) adds the rows
-      // cc, cc + 5, ... < nr in order (address r0' * E + tid: consecutive words).  The last round leaves
-      // dU = sum_k dS_k in su (K = 1: round 0 already did).
-      constexpr int NROUND = K == 1 ? 2 : K + 2;
-#pragma unroll
-      for (int j = 0; j < NROUND; ++j) {
-        // round order: dw3 first, then dS_0 .. dS_{K-1}, then (K > 1) dU
-        if (live) {
-#pragma unroll
-          for (int aa = 0; aa < E; aa += 2) {
-            float o0 = 0.f, o1 = 0.f;
-            if (j == 0) {
-#pragma unroll
-              for (int k = 0; k < K; ++k) {
-                o0 = fmaf(dl[k], s[k][aa], o0);
-                o1 = fmaf(dl[k], s[k][aa + 1], o1);
-              }
-            } else {
-#pragma unroll
-              for (int k = 0; k < K; ++k) {
-                if (j - 1 == k || j == K + 1) {
-                  o0 += dl[k] * sw3[aa] * (1.f - s[k][aa] * s[k][aa]);
-                  o1 += dl[k] * sw3[aa + 1] * (1.f - s[k][aa + 1] * s[k][aa + 1]);
-                }
-              }
-            }
-            *reinterpret_cast<float2*>(urow + aa) = make_float2(o0, o1);
-          }
-        }
-        __syncthreads();
-        if (j <= K) {
-          if (tid < NCH * E) {
-            float acc = col[j == 0 ? K : j - 1];
-            for (int rr = cc; rr < nr; rr += NCH) acc += su[rr * E + ca];
-            col[j == 0 ? K : j - 1] = acc;
-          }
-          if (j + 1 < NROUND) __syncthreads();  // su is rewritten by the next round
-        }
-      }
-      // ---- dW1 += dU^T V: lane (parity wg, block wa0, we0) over the rows wg, wg + 2, ... < nr
-      if (tid < 200) {
-        for (int rr = wg; rr < nr; rr += 2) {
-          float du[5], vv[5];
-#pragma unroll
-          for (int i = 0; i < 5; ++i) {
-            du[i] = su[rr * E + wa0 + i];
-            vv[i] = sv[rr * E + we0 + i];
-          }
-#pragma unroll
-          for (int i = 0; i < 5; ++i)
-#pragma unroll
-            for (int j = 0; j < 5; ++j) w1a[i][j] = fmaf(du[i], vv[j], w1a[i][j]);
-        }
-      }
-      // ---- dV = dU W1 for the own row (registers), then over sv once every lane is done reading it
-      float dv[E];
-      if (Db && live) {
-#pragma unroll
-        for (int e = 0; e < E; ++e) dv[e] = 0.f;
-#pragma unroll 2
-        for (int aa = 0; aa < E; ++aa) {
-          const float du = urow[aa];
-          const float* w = W1 + aa * E;
-#pragma unroll
-          for (int e = 0; e < E; ++e) dv[e] = fmaf(du, w[e], dv[e]);
-        }
-      }
-      if (Db) {
-        __syncthreads();
-        if (live) {
-#pragma unroll
-          for (int e = 0; e < E; e += 2) {
-            if constexpr (MODE == GRAD) {  // dPre = dV (1 - V^2)
-              const float2 vv = *reinterpret_cast<const float2*>(vrow + e);
-              *reinterpret_cast<float2*>(vrow + e) =
-                  make_float2(dv[e] * (1.f - vv.x * vv.x), dv[e + 1] * (1.f - vv.y * vv.y));
-            } else {
-              *reinterpret_cast<float2*>(vrow + e) = make_float2(dv[e], dv[e + 1]);
-            }
-          }
-        }
-        __syncthreads();
-        float* dst = Db + (long long)r0 * E;
-        const int n = nr * E;
-        if constexpr (MODE == GRAD) {
-          if (((uintptr_t)dst & 15) == 0) {
-            const int n4 = n >> 2;
-            for (int i = tid; i < n4; i += NT) reinterpret_cast<float4*>(dst)[i] = reinterpret_cast<const float4*>(sv)[i];
-            for (int i = (n4 << 2) + tid; i < n; i += NT) dst[i] = sv[i];
-          } else {
-            for (int i = tid; i < n; i += NT) dst[i] = sv[i];
-          }
-        } else {  // the module-level dV accumulates (each element has one writer)
-          for (int i = tid; i < n; i += NT) dst[i] += sv[i];
-        }
-      }
-    }
-  }
-
-  // ---- block reductions, fixed order
-  if constexpr (FUSED) {
-    __syncthreads();
-#pragma unroll
-    for (int i = 0; i < K * K + 1; ++i) {
-      const float t = wave_sum(cost[i]);
-      if (lane == 0) sred[wave][i] = t;
-    }
-    __syncthreads();
-    float* pl = a.part_loss + ((long long)b * a.nblk + blockIdx.x) * (K * K + 1);
-    if (tid < K * K + 1) pl[tid] = sred[0][tid] + sred[1][tid] + sred[2][tid] + sred[3][tid];
-  }
-  if constexpr (BWD) {
-    float* pr = a.part + ((long long)b * a.nblk + blockIdx.x) * rec_floats(K);
-    if (tid < 200) {
-#pragma unroll
-      for (int i = 0; i < 5; ++i)
-#pragma unroll
-        for (int j = 0; j < 5; ++j) pr[wg * E * E + (wa0 + i) * E + we0 + j] = w1a[i][j];
-    }
-    __syncthreads();
-    if (tid < NCH * E) {
-#pragma unroll
-      for (int j = 0; j < K + 1; ++j) scol[(cc * (K + 1) + j) * E + ca] = col[j];
-    }
-    __syncthreads();
-    if (tid < (K + 1) * E) {  // [dp_0 .. dp_{K-1} | dw3], classes 0..4 in order
-      float acc = 0.f;
-#pragma unroll
-      for (int c = 0; c < NCH; ++c) acc += scol[c * (K + 1) * E + tid];
-      pr[W1P + tid] = acc;
-    }
-  }
+// align_kernel with bf16 V (VB: a.V unused) and / or bf16 dPre at a row pitch (DB: a.dPre unused), compile-time
+// forms of the same text: the arithmetic, the tiles and the order of every sum are align_kernel's, so the COST
+// pass's partials on bf16 V equal, bit for bit, those on the same values in fp32
+template <int K, int MODE, bool VB, bool DB>
+__global__ __launch_bounds__(NT) void align_io_kernel(AlignArgs a, AlignIO io, const float* __restrict__ W1,
+                                                       const float* __restrict__ W2, const float* __restrict__ w3) {
+#include "attn_align_body.h"
 }
 
 // Finalize, stage 1: the dW1 (even + odd rows) and dw3 columns of the N block records, record groups
@@ -451,6 +187,17 @@ int launch_align(int K, const AlignArgs& a, const float* W1, const float* W2, co
   return 0;
 }
 
+template <int MODE, bool VB, bool DB>
+int launch_align_io(int K, const AlignArgs& a, const AlignIO& io, const float* W1, const float* W2, const float* w3,
+                    hipStream_t st) {
+  dim3 grid(a.nblk, a.B);
+  if (K == 1) hipLaunchKernelGGL((align_io_kernel<1, MODE, VB, DB>), grid, dim3(NT), 0, st, a, io, W1, W2, w3);
+  if (K == 2) hipLaunchKernelGGL((align_io_kernel<2, MODE, VB, DB>), grid, dim3(NT), 0, st, a, io, W1, W2, w3);
+  if (K == 3) hipLaunchKernelGGL((align_io_kernel<3, MODE, VB, DB>), grid, dim3(NT), 0, st, a, io, W1, W2, w3);
+  DL4SS_CHECK_LAUNCH();
+  return 0;
+}
+
 int finalize(const float* part, int B, int K, int nblk, const float* q, long long qs, const float* W2, float* dq,
              long long dqs, float* dW1, float* dW2, float* dw3, hipStream_t st) {
   const int rec = rec_floats(K), N = B * nblk;
@@ -526,6 +273,49 @@ DL4SS_API int dl4ss_mask_attn_align_loss(int pass, int B, int K, int T, int F, i
   a.mask_out = mask_out; a.ms = (long long)K * R; a.pred_out = pred_out;
   return pass == 1 ? launch_align<GRAD>(K, a, W1, W2, w3, as_stream(stream))
                    : launch_align<COST>(K, a, W1, W2, w3, as_stream(stream));
+}
+
+// dl4ss_mask_attn_align_loss with the bf16 step's I/O forms (include/dl4ss_align.h): V or V_bf16, dPre or
+// dPre_bf16 at a row pitch.  Every refusal comes before any launch.
+DL4SS_API int dl4ss_mask_attn_align_loss_ex(int pass, int B, int K, int T, int F, int E_, const float* V,
+                                            const void* V_bf16, const float* q, const float* W1, const float* W2,
+                                            const float* w3, const float* X, long long x_bstride, const float* Y,
+                                            long long y_bstride, long long y_kstride, const int* perm, float s1,
+                                            float s2, float* dPre, void* dPre_bf16, long long dpre_bf16_ld,
+                                            float* part_loss, float* part, long long part_floats_, float* mask_out,
+                                            float* pred_out, void* stream) {
+  DL4SS_REQUIRE(pass == 0 || pass == 1);
+  DL4SS_REQUIRE(B > 0 && K >= 1 && K <= 3 && T > 0 && F > 0 && E_ == E);
+  DL4SS_REQUIRE((V != nullptr) != (V_bf16 != nullptr));
+  DL4SS_REQUIRE(((uintptr_t)V_bf16 & 3) == 0);
+  DL4SS_REQUIRE(q && W1 && W2 && w3 && X && Y && part_loss);
+  const long long R = (long long)T * F;
+  DL4SS_REQUIRE(R <= 0x7fffffff / E && x_bstride >= R && y_kstride >= R && y_bstride >= R);
+  // (checked in the COST pass too, which is handed the GRAD pass's pointers and writes to neither)
+  DL4SS_REQUIRE(!dPre_bf16 || (dpre_bf16_ld >= (long long)F * E && dpre_bf16_ld % 2 == 0 &&
+                               ((uintptr_t)dPre_bf16 & 3) == 0));
+  const int nblk = align_nblk(R);
+  if (pass == 1) {
+    DL4SS_REQUIRE((dPre != nullptr) != (dPre_bf16 != nullptr));
+    DL4SS_REQUIRE(!(V_bf16 && dPre));  // bf16 V with fp32 dPre: no step forms it, not built
+    DL4SS_REQUIRE(part && part_floats_ >= part_floats(B, K, nblk));
+  }
+  AlignArgs a{};
+  a.B = B; a.R = (int)R; a.nblk = nblk;
+  a.V = V; a.q = q; a.qs = (long long)K * E;
+  a.X = X; a.xs = x_bstride; a.Y = Y; a.ys = y_bstride; a.yks = y_kstride;
+  a.perm = perm; a.s1 = s1; a.s2 = s2; a.dPre = pass == 1 ? dPre : nullptr; a.part_loss = part_loss; a.part = part;
+  a.mask_out = mask_out; a.ms = (long long)K * R; a.pred_out = pred_out;
+  AlignIO io{};
+  io.Vb = static_cast<const unsigned short*>(V_bf16);
+  io.dPreB = static_cast<unsigned short*>(dPre_bf16); io.ldpb = dpre_bf16_ld; io.T = T; io.F = F;
+  hipStream_t st = as_stream(stream);
+  if (pass == 0)
+    return V_bf16 ? launch_align_io<COST, true, false>(K, a, io, W1, W2, w3, st)
+                  : launch_align<COST>(K, a, W1, W2, w3, st);
+  if (dPre) return launch_align<GRAD>(K, a, W1, W2, w3, st);  // fp32 V, fp32 dPre: dl4ss_mask_attn_align_loss
+  return V_bf16 ? launch_align_io<GRAD, true, true>(K, a, io, W1, W2, w3, st)
+                : launch_align_io<GRAD, false, true>(K, a, io, W1, W2, w3, st);
 }
 
 // dq (B, K, E), dW1 (E, E), dW2 (E, E), dw3 (E) from the GRAD pass's partial records, fixed order

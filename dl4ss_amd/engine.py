@@ -92,8 +92,9 @@ class SepTrainer:
         self.mode, self.precision = mode, precision
         # split-K of the fp32 step's backward GEMMs (gemm.hip: fp32 atomics, the order of the partial sums
         # varies from launch to launch).  The 'align' step keeps every GEMM in one piece instead, so that its
-        # gradients are bitwise reproducible, eager or replayed
-        self._sk = 1 if self.align else "auto"
+        # gradients are bitwise reproducible, eager or replayed.  (The bf16 steps never read _sk: their gemm_gl
+        # split-K is deterministic, and an align net keeps the usual split factors there.)
+        self._sk = 1 if (self.align and not self.fast) else "auto"
         # splitk_reduce "fixed" (fp32): every backward GEMM splits ("auto", 'align' too) through fp32 slabs added
         # in a fixed order (ops.gemm(reduce="fixed")) and the bias gradients are fixed-order column sums
         # (ops.vp_colsum): the whole step repeats bit for bit.  Both workspaces are allocated below
@@ -446,15 +447,20 @@ class SepTrainer:
                   Y=ptr(Y), y_bstride=ys, y_kstride=yks, perm=ptr(perm), s1=self.s1, s2=self.s2,
                   part_loss=ptr(self.part_loss), mask_out=ptr(mask_out), pred_out=ptr(pred_out),
                   stream=_lib.stream_ptr())
-        if self.align and gext is None:
-            net = self.net
-            _lib.call("dl4ss_mask_attn_align_loss", pass_=pass_, V=ptr(self.V),
-                      W1=ptr(net.view("att.Linear_1.weight")), W2=ptr(net.view("att.Linear_2.weight")),
-                      w3=ptr(net.view("att.Linear_3.weight")), dPre=ptr(self.V) if grad else None,
-                      part=ptr(self.part_att) if grad else None, part_floats=self.part_att.numel(), **kw)
-            return
         # bf16 path: V itself is bf16 (the Linear's EPI_TANH_BF16 epilogue); bf16s: fp32 V, bf16 dPre
         bf16v = self.fast and not self.split
+        if self.align and gext is None:
+            net = self.net
+            akw = dict(pass_=pass_, W1=ptr(net.view("att.Linear_1.weight")), W2=ptr(net.view("att.Linear_2.weight")),
+                       w3=ptr(net.view("att.Linear_3.weight")), part=ptr(self.part_att) if grad else None,
+                       part_floats=self.part_att.numel(), **kw)
+            if self.fast:  # the same kernel text on bf16 V (bf16) or fp32 V (bf16s), dPre into the GEMMs' bf16 rows
+                _lib.call("dl4ss_mask_attn_align_loss_ex", V=None if bf16v else ptr(self.V),
+                          V_bf16=ptr(self.Vb) if bf16v else None, dPre=None, dPre_bf16=ptr(self.dPreb),
+                          dpre_bf16_ld=self.dPreb.stride(0), **akw)
+            else:
+                _lib.call("dl4ss_mask_attn_align_loss", V=ptr(self.V), dPre=ptr(self.V) if grad else None, **akw)
+            return
         kw["V_bf16" if bf16v else "V"] = ptr(self.Vb if bf16v else self.V)
         # (the COST pass gets dPre_bf16 too: it selects the same attention kernel as the GRAD pass)
         kw.update(dPre_bf16=ptr(self.dPreb) if self.fast else None,
@@ -483,7 +489,7 @@ class SepTrainer:
         if self.align:
             # the loss from the same partials; dq and the three attention-weight gradients from the align
             # partials, straight into their views of the flat gradient (backward_early zeroes only the
-            # range in front of them)
+            # range in front of them; the bf16 steps zero nothing: each of the four has this one writer)
             net, g = self.net, self.net.grad
             _lib.call("dl4ss_loss_finalize", part_loss=_lib.ptr(self.part_loss), B=self.B, K=self.K, nblk=self.nblk,
                       perm=_lib.ptr(perm), s1=self.s1, s2=self.s2, loss_out=_lib.ptr(self.loss), part_dq=None, qw=net.W,
@@ -693,9 +699,13 @@ class SepTrainer:
         SepNet.bucket_split on) is complete when this returns (in stream order)."""
         net, H = self.net, self.net.H
         g = net.grad
-        if self.align:  # the attention-weight gradients behind this range were written by loss_and_grad
+        # (zero_free, the grouped bf16 backward: every gradient has one writer per step, 'align' included -- the
+        # finalize in loss_and_grad WRITES dq and the three attention-weight gradients -- so nothing is zeroed)
+        if self.zero_free:
+            pass
+        elif self.align:  # the attention-weight gradients behind this range were written by loss_and_grad
             g[:net.offsets["att.Linear_1.weight"][0]].zero_()
-        elif not self.zero_free:
+        else:
             g.zero_()
         self._query_bwd()
         if self.fast:

@@ -157,9 +157,14 @@ def check_args(net, batch, k, n_samples, mode, precision, rnn_precision, loss_ch
             raise ValueError("attention='align' supports the modes 'label' and 'pit', not 'crm'")
         if loss_channels:
             raise ValueError("attention='align' does not support loss_channels")
-        if precision in ("bf16s", "bf16s2") or (precision == "bf16" and (rnn_precision or precision) == "bf16"):
-            raise ValueError(f"attention='align' is not built for the bf16 / bf16s fast paths "
-                             f"(precision={precision!r}, rnn_precision={rnn_precision!r}); use precision='fp32'")
+        # precision "bf16" / "bf16s" / "bf16s2" on the bf16 recurrence: the fast step, with the align kernel's
+        # bf16-V / bf16-dPre forms (dl4ss_mask_attn_align_loss_ex) -- built and verified for the BiLSTM nets, the
+        # cell of the Keras model that builds 'align'; a BiGRU align net stays on the fp32 step
+        fast = precision in ("bf16s", "bf16s2") or (precision == "bf16" and (rnn_precision or precision) == "bf16")
+        if fast and net.cell != "lstm":
+            raise ValueError(f"attention='align' on the bf16 / bf16s fast paths is built for cell 'lstm', not "
+                             f"{net.cell!r} (precision={precision!r}, rnn_precision={rnn_precision!r}); use "
+                             "precision='fp32'")
         if net.E != 50:
             raise ValueError("attention='align' is built for embedding size 50")
     return clip_norm, adv_clip_norm

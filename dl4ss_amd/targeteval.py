@@ -89,7 +89,7 @@ class TargetEvaluator:
     the background clip, prepared once (prepare_background).  ``log_features``: the net reads log magnitudes
     (IS_LOG_SPECTRAL), the mask still multiplies the magnitudes.  ``precision``: the mask net's, as
     ``MaskNetForward``; with "bf16" the attention reads V rounded to bf16, as the bf16 training step's does (not
-    with 'align', whose kernel reads fp32 V).
+    with 'align': the evaluator feeds its kernel the fp32 V, where the bf16 training step feeds it bf16 V).
 
     ``evaluate`` and ``eval_loss`` enqueue launches only: nothing synchronises with the host.  ``check()`` does,
     and raises if a recurrence hand-off timed out; ``summary()`` reads the running sums."""
