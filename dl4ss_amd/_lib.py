@@ -1,12 +1,14 @@
-"""ctypes binding of ``libdl4ss_hip.so``, derived from the C ABI's one declaration, ``include/dl4ss_hip.h``
-(and ``include/dl4ss_imgq.h``, the image-query encoder's entry points, ``include/dl4ss_optim.h``, Nadam and
-Keras's clipnorm, ``include/dl4ss_eval.h``, the target-speaker evaluation, and ``include/dl4ss_align.h``, ATTENTION 'align' on the
-bf16 steps, parsed the same way into ``IMGQ_*``, ``OPTIM_*``, ``EVAL_*`` and ``ALIGN_*`` tables).
+"""ctypes binding of ``libdl4ss_hip.so``, derived from the C ABI's one declaration: the public headers, every
+``*.h`` file of ``include/``.  ``CORE_HEADER`` comes first and the library must define every entry point it
+declares; an entry point of any other header is bound when the library has it and skipped when not, so a header
+added to ``include/`` is bound with no change here.
 
-The header is parsed once at import: every prototype gives the entry point's ``argtypes`` (``SIGNATURES``), its
-``restype`` (``RESTYPES``) and its parameter names (``PARAMS``); every enum constant and ``#define DL4SS_* <integer>``
-lands in ``CONSTANTS``.  The same header is compiled against every definition (``csrc/common.h`` includes it), so
-the binding, the prototypes and the definitions cannot drift apart.  A declaration the parser cannot fully
+Each header is parsed once at import into a ``Header``, kept by file name in ``HEADERS``, and ``merge_headers`` folds
+them into one namespace, refusing an entry point or a constant that two headers declare: every prototype gives the
+entry point's ``argtypes`` (``SIGNATURES``), its ``restype`` (``RESTYPES``) and its parameter names (``PARAMS``);
+every enum constant and ``#define DL4SS_* <integer>`` lands in ``CONSTANTS``.  A header is compiled against the
+definitions it declares (``csrc/common.h`` includes the core one, a source with a header of its own includes that),
+so the binding, the prototypes and the definitions cannot drift apart.  A declaration the parser cannot fully
 classify raises at import, with the offending text: it never guesses.
 
 ``call`` and ``query`` take positional arguments, then keywords by the header's parameter names (``pass_`` and
@@ -17,6 +19,7 @@ The product path has no CPU fallback: if the library is missing or a call return
 raises ``RuntimeError`` with the HIP error string.  Tensors are passed as raw device pointers; every call is
 enqueued on torch's current HIP stream.
 """
+import collections
 import ctypes
 import keyword
 import os
@@ -26,11 +29,8 @@ import torch
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("DL4SS_LIB", os.path.join(_HERE, "libdl4ss_hip.so"))
-HEADER = os.path.join(os.path.dirname(_HERE), "include", "dl4ss_hip.h")
-IMGQ_HEADER = os.path.join(os.path.dirname(_HERE), "include", "dl4ss_imgq.h")  # the image-query encoder's entry points
-OPTIM_HEADER = os.path.join(os.path.dirname(_HERE), "include", "dl4ss_optim.h")  # Nadam, Keras's clipnorm
-EVAL_HEADER = os.path.join(os.path.dirname(_HERE), "include", "dl4ss_eval.h")  # BSS Eval 2.0 gains, the eval mixture
-ALIGN_HEADER = os.path.join(os.path.dirname(_HERE), "include", "dl4ss_align.h")  # 'align' attention, bf16 V / dPre
+INCLUDE = os.path.join(os.path.dirname(_HERE), "include")
+CORE_HEADER = "dl4ss_hip.h"  # the one header whose every entry point the library must define
 
 P = ctypes.c_void_p
 I = ctypes.c_int
@@ -44,6 +44,9 @@ _POINTEE = set(_VALUE) | {"void", "double"}  # what a pointer or array parameter
 _RETURN = {"int": I, "long long": LL, "void": None}
 _PROTO = re.compile(r"(int|long long|void)\s+(dl4ss_\w+)\s*\(([^()]*)\)\s*;")
 _INT = r"(0[xX][0-9a-fA-F]+|\d+)"
+
+
+Header = collections.namedtuple("Header", "signatures restypes params constants")
 
 
 def parse_header(text, name="dl4ss_hip.h"):
@@ -85,35 +88,31 @@ def parse_header(text, name="dl4ss_hip.h"):
     return sigs, res, params, consts
 
 
-with open(HEADER) as _f:
-    SIGNATURES, RESTYPES, PARAMS, CONSTANTS = parse_header(_f.read())
-# the second public header, in tables of its own: SIGNATURES / RESTYPES / PARAMS / exported_symbols() stay what
-# dl4ss_hip.h declares
-with open(IMGQ_HEADER) as _f:
-    IMGQ_SIGNATURES, IMGQ_RESTYPES, IMGQ_PARAMS, IMGQ_CONSTANTS = parse_header(_f.read(), "dl4ss_imgq.h")
-if set(IMGQ_SIGNATURES) & set(SIGNATURES):
-    raise ValueError(f"dl4ss_imgq.h declares again: {sorted(set(IMGQ_SIGNATURES) & set(SIGNATURES))}")
-# the third, likewise
-with open(OPTIM_HEADER) as _f:
-    OPTIM_SIGNATURES, OPTIM_RESTYPES, OPTIM_PARAMS, OPTIM_CONSTANTS = parse_header(_f.read(), "dl4ss_optim.h")
-if set(OPTIM_SIGNATURES) & (set(SIGNATURES) | set(IMGQ_SIGNATURES)):
-    raise ValueError("dl4ss_optim.h declares again: "
-                     f"{sorted(set(OPTIM_SIGNATURES) & (set(SIGNATURES) | set(IMGQ_SIGNATURES)))}")
-# the fourth
-with open(EVAL_HEADER) as _f:
-    EVAL_SIGNATURES, EVAL_RESTYPES, EVAL_PARAMS, EVAL_CONSTANTS = parse_header(_f.read(), "dl4ss_eval.h")
-_EARLIER = set(SIGNATURES) | set(IMGQ_SIGNATURES) | set(OPTIM_SIGNATURES)
-if set(EVAL_SIGNATURES) & _EARLIER:
-    raise ValueError(f"dl4ss_eval.h declares again: {sorted(set(EVAL_SIGNATURES) & _EARLIER)}")
-# the fifth
-with open(ALIGN_HEADER) as _f:
-    ALIGN_SIGNATURES, ALIGN_RESTYPES, ALIGN_PARAMS, ALIGN_CONSTANTS = parse_header(_f.read(), "dl4ss_align.h")
-if set(ALIGN_SIGNATURES) & (_EARLIER | set(EVAL_SIGNATURES)):
-    raise ValueError(f"dl4ss_align.h declares again: {sorted(set(ALIGN_SIGNATURES) & (_EARLIER | set(EVAL_SIGNATURES)))}")
-_ALL_PARAMS = {**PARAMS, **IMGQ_PARAMS, **OPTIM_PARAMS, **EVAL_PARAMS, **ALIGN_PARAMS}
+def merge_headers(parsed):
+    """The one namespace of ``parsed`` (file name -> ``Header``, in order): ``ValueError`` for an entry point or a
+    constant that a second header declares, naming it and both headers."""
+    merged, first = Header({}, {}, {}, {}), {}
+    for name, header in parsed.items():
+        for symbol in (*header.signatures, *header.constants):
+            if symbol in first:
+                raise ValueError(f"{name} declares {symbol} again: {first[symbol]} has it")
+            first[symbol] = name
+        for table, part in zip(merged, header):
+            table.update(part)
+    return merged
+
+
+def _parse(name):
+    with open(os.path.join(INCLUDE, name)) as f:
+        return Header(*parse_header(f.read(), name))
+
+
+HEADERS = {name: _parse(name) for name in
+           [CORE_HEADER] + sorted(f for f in os.listdir(INCLUDE) if f.endswith(".h") and f != CORE_HEADER)}
+SIGNATURES, RESTYPES, PARAMS, CONSTANTS = merge_headers(HEADERS)
 # keyword -> slot of every entry point (a header name that is a Python keyword takes a trailing underscore)
 _SLOTS = {name: {p + "_" if keyword.iskeyword(p) else p: i for i, p in enumerate(ps)}
-          for name, ps in _ALL_PARAMS.items()}
+          for name, ps in PARAMS.items()}
 # knobs the library itself used to read from the environment, retired with plan.RETIRED_KNOBS
 RETIRED_ENV = ("DL4SS_ATTN_TILES", "DL4SS_RNN_MAX_WG", "DL4SS_RNN_MIN_BC")
 
@@ -132,21 +131,16 @@ def _load():
             f"dl4ss HIP library not found at {LIB_PATH}; run `python -m dl4ss_amd.build` "
             "(there is no CPU fallback)")
     lib = ctypes.CDLL(LIB_PATH)
-    for name, argtypes in SIGNATURES.items():
-        fn = getattr(lib, name)
-        fn.argtypes = argtypes
-        fn.restype = RESTYPES[name]
-    # the second to fifth headers' entry points.  A library without them still loads: the binding tests stand a
-    # stub with the first header's names alone in for the library, and DL4SS_LIB may name a build from before
-    # imgq.hip, optim.hip, targeteval.hip or the bf16 'align' forms.  Calling one that is missing fails in ctypes' own lookup, with the symbol's name:
-    # there is no other path
-    for sigs, restypes in ((IMGQ_SIGNATURES, IMGQ_RESTYPES), (OPTIM_SIGNATURES, OPTIM_RESTYPES),
-                           (EVAL_SIGNATURES, EVAL_RESTYPES), (ALIGN_SIGNATURES, ALIGN_RESTYPES)):
-        for name, argtypes in sigs.items():
-            fn = getattr(lib, name, None)
+    # an entry point of the core header must resolve.  One of another header is bound when the library has it: the
+    # binding tests stand a stub with the core header's names alone in for the library, and DL4SS_LIB may name a
+    # build from before that header's source.  Calling one that is missing fails in ctypes' own lookup, with the
+    # symbol's name: there is no other path
+    for header_name, header in HEADERS.items():
+        for name, argtypes in header.signatures.items():
+            fn = getattr(lib, name) if header_name == CORE_HEADER else getattr(lib, name, None)
             if fn is not None:
                 fn.argtypes = argtypes
-                fn.restype = restypes[name]
+                fn.restype = header.restypes[name]
     hip = ctypes.CDLL("libamdhip64.so")
     hip.hipGetErrorString.restype = ctypes.c_char_p
     hip.hipGetErrorString.argtypes = [ctypes.c_int]
@@ -159,24 +153,9 @@ def lib():
     return _load()
 
 
-def exported_symbols():
-    return list(SIGNATURES)
-
-
-def imgq_exported_symbols():
-    return list(IMGQ_SIGNATURES)
-
-
-def optim_exported_symbols():
-    return list(OPTIM_SIGNATURES)
-
-
-def eval_exported_symbols():
-    return list(EVAL_SIGNATURES)
-
-
-def align_exported_symbols():
-    return list(ALIGN_SIGNATURES)
+def exported_symbols(header=None):
+    """Every declared entry point, or those of the one header (a file name) given."""
+    return list(SIGNATURES if header is None else HEADERS[header].signatures)
 
 
 def stream_ptr(stream=None):
@@ -202,11 +181,10 @@ def bind(name, args, kw):
     ``TypeError`` unless every parameter of the prototype is given exactly once."""
     slots = _SLOTS.get(name)
     if slots is None:
-        raise TypeError(f"{name} is not declared in include/dl4ss_hip.h, include/dl4ss_imgq.h, "
-                        "include/dl4ss_optim.h, include/dl4ss_eval.h or include/dl4ss_align.h")
+        raise TypeError(f"{name} is not declared in " + ", ".join("include/" + h for h in HEADERS))
     n, given = len(slots), len(args) + len(kw)
     if len(args) > n:
-        raise TypeError(f"{name} takes {n} arguments (the last is {_ALL_PARAMS[name][-1]!r}), {given} given")
+        raise TypeError(f"{name} takes {n} arguments (the last is {PARAMS[name][-1]!r}), {given} given")
     if not kw and given == n:
         return tuple(args)
     out = list(args) + [None] * (n - len(args))

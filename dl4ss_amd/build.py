@@ -3,13 +3,12 @@
 Every ``dl4ss_amd/csrc/*.hip`` is compiled to an object with
 ``hipcc --offload-arch=gfx950 -O3 -fPIC`` (in parallel) and linked into one
 shared library next to this file.  The library exports the C ABI declared in
-``include/dl4ss_hip.h``: every source includes that header (through
-``csrc/common.h``), so a definition that disagrees with its prototype fails to
-compile; ``include/dl4ss_imgq.h`` declares the image-query encoder's entry points
-and ``csrc/imgq.hip`` includes it in the same way, as ``csrc/optim.hip`` does ``include/dl4ss_optim.h`` (Nadam and
-Keras's clipnorm) and ``csrc/targeteval.hip`` ``include/dl4ss_eval.h`` (the target-speaker evaluation) and ``csrc/attn_align.hip``
-``include/dl4ss_align.h`` ('align' attention on the bf16 steps).  Objects are rebuilt only when a source or header -- the public one
-included -- is newer than the object.
+the public headers, the ``*.h`` files of ``include/``: every source includes
+the core one, ``dl4ss_hip.h`` (through ``csrc/common.h``), and a source whose
+entry points have a header of their own includes that one too, so a definition
+that disagrees with its prototype fails to compile.  Objects are rebuilt only
+when a source or header -- every public one included -- is newer than the
+object.
 """
 import concurrent.futures as cf
 import os
@@ -20,11 +19,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 OBJ = os.path.join(HERE, "csrc", "_obj")
 LIB = os.path.join(HERE, "libdl4ss_hip.so")
-HEADER = os.path.join(os.path.dirname(HERE), "include", "dl4ss_hip.h")  # (common.h includes it by relative path)
-IMGQ_HEADER = os.path.join(os.path.dirname(HERE), "include", "dl4ss_imgq.h")  # (imgq.hip includes it the same way)
-OPTIM_HEADER = os.path.join(os.path.dirname(HERE), "include", "dl4ss_optim.h")  # (optim.hip likewise)
-EVAL_HEADER = os.path.join(os.path.dirname(HERE), "include", "dl4ss_eval.h")  # (targeteval.hip likewise)
-ALIGN_HEADER = os.path.join(os.path.dirname(HERE), "include", "dl4ss_align.h")  # (attn_align.hip likewise)
+INCLUDE = os.path.join(os.path.dirname(HERE), "include")  # (the sources include its headers by relative path)
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 ARCH = "gfx950"
 FLAGS = ["-O3", "-fPIC", "-std=c++17", f"--offload-arch={ARCH}", "-munsafe-fp-atomics",
@@ -54,8 +49,7 @@ def _compile(src, obj):
 def build(verbose=False, jobs=None):
     os.makedirs(OBJ, exist_ok=True)
     srcs = sorted(f for f in os.listdir(CSRC) if f.endswith(".hip"))
-    headers = [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".h")]
-    headers += [HEADER, IMGQ_HEADER, OPTIM_HEADER, EVAL_HEADER, ALIGN_HEADER]
+    headers = [os.path.join(d, f) for d in (CSRC, INCLUDE) for f in os.listdir(d) if f.endswith(".h")]
     objs, todo = [], []
     for f in srcs:
         src = os.path.join(CSRC, f)

@@ -27,7 +27,7 @@ class ImageQueryNet(FlatParams):
 
     def __init__(self, image_size=(28, 28), emb=50, device="cuda", seed=1):
         h, w = (int(x) for x in image_size)
-        c = _lib.IMGQ_CONSTANTS
+        c = _lib.CONSTANTS
         lo, hi = c["DL4SS_IMGQ_MIN_HW"], c["DL4SS_IMGQ_MAX_HW"]
         if not (lo <= h <= hi and lo <= w <= hi):
             raise ValueError(f"ImageQueryNet: images of {h} x {w}, expected {lo} <= h, w <= {hi}")
@@ -85,7 +85,7 @@ class ImageQueryEncoder:
     def __init__(self, inet, n):
         if not isinstance(inet, ImageQueryNet):
             raise ValueError("ImageQueryEncoder: expected an ImageQueryNet")
-        n_max = _lib.IMGQ_CONSTANTS["DL4SS_IMGQ_MAX_N"]
+        n_max = _lib.CONSTANTS["DL4SS_IMGQ_MAX_N"]
         if not 1 <= n <= n_max:
             raise ValueError(f"ImageQueryEncoder: 1 <= n <= {n_max}")
         self.net, self.n = inet, int(n)

@@ -10,7 +10,7 @@ import torch
 
 from . import _lib
 
-_C = _lib.CONSTANTS  # the enums and flag macros of include/dl4ss_hip.h
+_C = _lib.CONSTANTS  # the enums and flag macros of the public headers
 STFT_COMPLEX, STFT_MAG, STFT_LOGMAG, STFT_CONJ = (_C["DL4SS_STFT_" + n] for n in ("COMPLEX", "MAG", "LOGMAG", "CONJ"))
 N_FFT, HOP = 256, 128
 F_BINS = N_FFT // 2 + 1
@@ -437,9 +437,9 @@ def check_clip_norm(x, name="clip_norm"):
     return x
 
 
-CLIP_TORCH, CLIP_KERAS = (_lib.OPTIM_CONSTANTS[k] for k in ("DL4SS_CLIP_TORCH", "DL4SS_CLIP_KERAS"))
-CLIP_MAX_PARTS = _lib.OPTIM_CONSTANTS["DL4SS_CLIP_MAX_PARTS"]
-STATUS_NONFINITE_GRAD = _lib.OPTIM_CONSTANTS["DL4SS_STATUS_NONFINITE_GRAD"]  # the sticky bit of status[0]
+CLIP_TORCH, CLIP_KERAS = (_C[k] for k in ("DL4SS_CLIP_TORCH", "DL4SS_CLIP_KERAS"))
+CLIP_MAX_PARTS = _C["DL4SS_CLIP_MAX_PARTS"]
+STATUS_NONFINITE_GRAD = _C["DL4SS_STATUS_NONFINITE_GRAD"]  # the sticky bit of status[0]
 
 
 def _clip_args(clip, n, name, n_part=None):
@@ -823,9 +823,8 @@ def imgq_param_count(h, w, E):
     """Floats in the image-query encoder's parameter block for (h, w) images and E outputs."""
     P = _lib.query("dl4ss_imgq_param_count", h=int(h), w=int(w), E=int(E))
     if P < 0:
-        c = _lib.IMGQ_CONSTANTS
-        raise ValueError(f"image query: images of {h} x {w} with E = {E}: {c['DL4SS_IMGQ_MIN_HW']} <= h, w <= "
-                         f"{c['DL4SS_IMGQ_MAX_HW']} and 1 <= E <= {c['DL4SS_IMGQ_MAX_E']}")
+        raise ValueError(f"image query: images of {h} x {w} with E = {E}: {_C['DL4SS_IMGQ_MIN_HW']} <= h, w <= "
+                         f"{_C['DL4SS_IMGQ_MAX_HW']} and 1 <= E <= {_C['DL4SS_IMGQ_MAX_E']}")
     return P
 
 
@@ -838,8 +837,8 @@ def _imgq_args(images, params, E, name):
     P = imgq_param_count(h, w, E)
     if params.numel() < P:
         raise RuntimeError(f"{name}: params holds {params.numel()} floats, the encoder has {P}")
-    if n > _lib.IMGQ_CONSTANTS["DL4SS_IMGQ_MAX_N"]:
-        raise RuntimeError(f"{name}: n <= {_lib.IMGQ_CONSTANTS['DL4SS_IMGQ_MAX_N']}")
+    if n > _C["DL4SS_IMGQ_MAX_N"]:
+        raise RuntimeError(f"{name}: n <= {_C['DL4SS_IMGQ_MAX_N']}")
     return n, h, w, P
 
 

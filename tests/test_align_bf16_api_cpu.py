@@ -12,6 +12,7 @@ from dl4ss_amd.voiceprint import SpeakerMemory, VoiceprintNet
 
 N = 4000
 ENTRY = "dl4ss_mask_attn_align_loss_ex"
+CORE, ALIGN = _lib.HEADERS["dl4ss_hip.h"], _lib.HEADERS["dl4ss_align.h"]
 
 
 def _net(**kw):
@@ -84,9 +85,8 @@ def test_hard_gates_align_net_runs_bf16_gemms_on_the_fp32_recurrence_only():
 def test_the_fifth_header_declares_the_entry_point_and_lib_binds_it():
     with open(os.path.join(ROOT, "include", "dl4ss_align.h")) as f:
         sigs, res, params, consts = _lib.parse_header(f.read(), "dl4ss_align.h")
-    assert set(sigs) == {ENTRY} == set(_lib.ALIGN_SIGNATURES) == set(_lib.align_exported_symbols())
-    assert (sigs, res, params, consts) == (_lib.ALIGN_SIGNATURES, _lib.ALIGN_RESTYPES, _lib.ALIGN_PARAMS,
-                                           _lib.ALIGN_CONSTANTS) and consts == {}
+    assert set(sigs) == {ENTRY} == set(ALIGN.signatures) == set(_lib.exported_symbols("dl4ss_align.h"))
+    assert (sigs, res, params, consts) == ALIGN and consts == {}
     P, I, LL, F = _lib.P, _lib.I, _lib.LL, _lib.F
     assert sigs[ENTRY] == [I, I, I, I, I, I, P, P, P, P, P, P, P, LL, P, LL, LL, P, F, F, P, P, LL, P, P, LL, P, P, P]
     assert res[ENTRY] is I
@@ -94,12 +94,15 @@ def test_the_fifth_header_declares_the_entry_point_and_lib_binds_it():
                              "Y", "y_bstride", "y_kstride", "perm", "s1", "s2", "dPre", "dPre_bf16", "dpre_bf16_ld",
                              "part_loss", "part", "part_floats", "mask_out", "pred_out", "stream")
     # the fp32 entry's parameters with the two bf16 ones of dl4ss_mask_attn_loss_ex / _bf16v added, same names
-    old = _lib.PARAMS["dl4ss_mask_attn_align_loss"]
+    old = CORE.params["dl4ss_mask_attn_align_loss"]
     assert tuple(p for p in params[ENTRY] if p not in ("V_bf16", "dPre_bf16", "dpre_bf16_ld")) == old
-    assert {"V_bf16", "dPre_bf16", "dpre_bf16_ld"} <= set(_lib.PARAMS["dl4ss_mask_attn_loss_bf16v"])
-    # no name of an earlier header comes back, and the first header's tables stay what dl4ss_hip.h declares
-    earlier = set(_lib.SIGNATURES) | set(_lib.IMGQ_SIGNATURES) | set(_lib.OPTIM_SIGNATURES) | set(_lib.EVAL_SIGNATURES)
-    assert ENTRY not in earlier and ENTRY not in _lib.exported_symbols()
+    assert {"V_bf16", "dPre_bf16", "dpre_bf16_ld"} <= set(CORE.params["dl4ss_mask_attn_loss_bf16v"])
+    # no other header has the name, and the first header's tables stay what dl4ss_hip.h declares
+    others = [h for name, h in _lib.HEADERS.items() if name != "dl4ss_align.h"]
+    assert len(others) >= 4 and not any(ENTRY in h.signatures for h in others)
+    assert ENTRY not in _lib.exported_symbols("dl4ss_hip.h") and ENTRY in _lib.exported_symbols()
+    with open(os.path.join(ROOT, "include", "dl4ss_hip.h")) as f:
+        assert CORE == _lib.parse_header(f.read())
     n = len(params[ENTRY])
     kw = {("pass_" if p == "pass" else p): i for i, p in enumerate(params[ENTRY])}
     assert _lib.bind(ENTRY, (), kw) == tuple(range(n))
@@ -111,7 +114,7 @@ def test_the_fifth_header_declares_the_entry_point_and_lib_binds_it():
 
 def test_the_library_exports_the_entry_point():
     fn = getattr(_lib.lib(), ENTRY)
-    assert fn.argtypes == _lib.ALIGN_SIGNATURES[ENTRY] and fn.restype is _lib.ALIGN_RESTYPES[ENTRY]
+    assert fn.argtypes == ALIGN.signatures[ENTRY] and fn.restype is ALIGN.restypes[ENTRY]
 
 
 class _Fake:
@@ -139,7 +142,7 @@ def test_trainer_routes_the_align_passes(precision, monkeypatch):
     for pass_, grad in ((0, False), (1, True)):
         tr.attn(pass_, tr.perm if grad else None)
         name, args = fake.calls[-1]
-        got = dict(zip(_lib._ALL_PARAMS[name], args))
+        got = dict(zip(_lib.PARAMS[name], args))
         assert got["pass"] == pass_ and got["E"] == 50 and got["part_floats"] == tr.part_att.numel()
         assert got["W1"] == tag(tr.net.view("att.Linear_1.weight")) and got["w3"] == tag(tr.net.view("att.Linear_3.weight"))
         assert got["part"] == (tag(tr.part_att) if grad else None) and got["perm"] == (tag(tr.perm) if grad else None)

@@ -16,6 +16,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 N = 4000  # 32 frames
 ENTRIES = {"dl4ss_imgq_param_count", "dl4ss_imgq_dense_in", "dl4ss_imgq_fwd", "dl4ss_imgq_bwd", "dl4ss_imgq_reduce",
            "dl4ss_imgq_guard"}
+CORE, IMGQ = _lib.HEADERS["dl4ss_hip.h"], _lib.HEADERS["dl4ss_imgq.h"]
 
 
 def _net(**kw):
@@ -35,8 +36,9 @@ def _mem(emb=50):
 def test_header_parses_and_the_library_exports_it():
     with open(os.path.join(ROOT, "include", "dl4ss_imgq.h")) as f:
         sigs, res, params, consts = _lib.parse_header(f.read())
-    assert set(sigs) == ENTRIES == set(_lib.IMGQ_SIGNATURES) == set(_lib.imgq_exported_symbols())
-    assert sigs == _lib.IMGQ_SIGNATURES and params == _lib.IMGQ_PARAMS and consts == _lib.IMGQ_CONSTANTS
+    assert set(sigs) == ENTRIES == set(IMGQ.signatures) == set(_lib.exported_symbols("dl4ss_imgq.h"))
+    assert (sigs, res, params, consts) == IMGQ
+    assert ENTRIES <= set(_lib.exported_symbols()) and consts.items() <= _lib.CONSTANTS.items()
     P, I, LL = _lib.P, _lib.I, _lib.LL
     assert sigs["dl4ss_imgq_fwd"] == [P, P, I, I, I, I, P, P]
     assert params["dl4ss_imgq_bwd"] == ("images", "dvec", "params", "n", "h", "w", "E", "dpart", "ld",
@@ -56,7 +58,7 @@ def test_header_parses_and_the_library_exports_it():
 
 
 def test_a_library_without_the_second_header_loads_and_a_call_names_the_symbol(monkeypatch):
-    """A stand-in with the first header's names alone (what tests/test_lib_bind_cpu.py binds) loads; an image-query
+    """A stand-in with the core header's names alone (what tests/test_lib_bind_cpu.py binds) loads; an image-query
     call on it fails in the symbol lookup, by name."""
     import types
 
@@ -66,7 +68,7 @@ def test_a_library_without_the_second_header_loads_and_a_call_names_the_symbol(m
 
     monkeypatch.setattr(_lib, "_lib", None)
     monkeypatch.setattr(_lib.ctypes, "CDLL", lambda path: Old(
-        hipGetErrorString=types.SimpleNamespace(), **{n: types.SimpleNamespace() for n in _lib.SIGNATURES}))
+        hipGetErrorString=types.SimpleNamespace(), **{n: types.SimpleNamespace() for n in CORE.signatures}))
     lib = _lib._load()
     assert lib.dl4ss_attn_nblk.argtypes == [_lib.I, _lib.I]
     with pytest.raises(AttributeError, match="dl4ss_imgq_param_count"):
@@ -78,16 +80,16 @@ def test_a_library_without_the_second_header_loads_and_a_call_names_the_symbol(m
 
 def test_first_header_tables_are_untouched():
     with open(os.path.join(ROOT, "include", "dl4ss_hip.h")) as f:
-        sigs, res, params, consts = _lib.parse_header(f.read())
-    assert (sigs, res, params, consts) == (_lib.SIGNATURES, _lib.RESTYPES, _lib.PARAMS, _lib.CONSTANTS)
-    assert not any(n.startswith("dl4ss_imgq_") for n in _lib.SIGNATURES)
-    assert not any(n.startswith("DL4SS_IMGQ_") for n in _lib.CONSTANTS)
-    assert _lib.exported_symbols() == list(_lib.SIGNATURES) and not ENTRIES & set(_lib.exported_symbols())
+        assert CORE == _lib.parse_header(f.read())
+    assert not any(n.startswith("dl4ss_imgq_") for n in CORE.signatures)
+    assert not any(n.startswith("DL4SS_IMGQ_") for n in CORE.constants)
+    assert _lib.exported_symbols("dl4ss_hip.h") == list(CORE.signatures)
+    assert not ENTRIES & set(_lib.exported_symbols("dl4ss_hip.h"))
 
 
 def test_bind_orders_keywords_and_refuses_unknown_names():
     want = ("im", "pa", 3, 28, 28, 50, "ve", "st")
-    kw = dict(zip(_lib.IMGQ_PARAMS["dl4ss_imgq_fwd"], want))
+    kw = dict(zip(IMGQ.params["dl4ss_imgq_fwd"], want))
     assert _lib.bind("dl4ss_imgq_fwd", (), dict(reversed(kw.items()))) == want
     assert _lib.bind("dl4ss_imgq_fwd", want[:2], {k: kw[k] for k in ("stream", "vec", "E", "w", "h", "n")}) == want
     with pytest.raises(TypeError, match="'vec'") as e:
@@ -125,7 +127,7 @@ def test_image_query_net_names_shapes_and_count():
     assert {k: tuple(t.shape) for k, t in inet.state_dict().items()} == want
     assert inet.num_params == 2418 == sum(t.numel() for _, t in inet.named_parameters())
     assert inet.numel == 2420 and inet.grad.shape == inet.flat.shape and tuple(inet.grad_view("img.conv2.bias").shape) == (8,)
-    c = _lib.IMGQ_CONSTANTS  # the flat layout is the kernels' parameter block
+    c = IMGQ.constants  # the flat layout is the kernels' parameter block
     assert inet.offsets["img.conv3.weight"][0] == c["DL4SS_IMGQ_OFF_W3"] == 400
     assert inet.offsets["img.dense.weight"][0] == c["DL4SS_IMGQ_OFF_WD"] == c["DL4SS_IMGQ_CONV_PARAMS"] == 1568
     assert inet.offsets["img.dense.bias"][0] == 1568 + 800

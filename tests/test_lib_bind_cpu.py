@@ -1,6 +1,7 @@
-"""The binding is derived from include/dl4ss_hip.h, and the header is compiled against the definitions (host only).
+"""The binding is derived from the headers of include/, and each is compiled against the definitions (host only).
 
-  * the derived SIGNATURES / RESTYPES equal the hand-written tables they replaced, kept below as the specification;
+  * the core header's derived signatures / restypes equal the hand-written tables they replaced, kept below as the
+    specification; the merged tables are the disjoint union of every header's;
   * the parser refuses what it cannot classify, naming the text;
   * a definition that disagrees with its prototype does not compile (and the true one does);
   * _lib.bind puts keywords into the header's order and refuses a wrong set of arguments with TypeError;
@@ -134,22 +135,46 @@ RESTYPES = {"dl4ss_birnn_workspace_bytes": ctypes.c_longlong, "dl4ss_colsum_bf16
             "dl4ss_debug_set_place_force": None, "dl4ss_debug_set_rnn_max_wg": None}
 
 
+CORE = _lib.HEADERS["dl4ss_hip.h"]
+
+
 def test_derived_tables_equal_the_hand_written_ones():
-    assert len(SIGNATURES) == 98 and sorted(_lib.SIGNATURES) == sorted(SIGNATURES)
+    assert len(SIGNATURES) == 98 and sorted(CORE.signatures) == sorted(SIGNATURES)
+    assert _lib.exported_symbols("dl4ss_hip.h") == list(CORE.signatures)
     for name, argtypes in SIGNATURES.items():
-        assert _lib.SIGNATURES[name] == argtypes, name
-        assert _lib.RESTYPES[name] == RESTYPES.get(name, ctypes.c_int), name  # (int: a hipError_t)
-        assert len(_lib.PARAMS[name]) == len(argtypes), name
+        assert CORE.signatures[name] == argtypes, name
+        assert CORE.restypes[name] == RESTYPES.get(name, ctypes.c_int), name  # (int: a hipError_t)
+        assert len(CORE.params[name]) == len(argtypes), name
+
+
+def test_merged_tables_are_the_disjoint_union_of_the_headers():
+    assert next(iter(_lib.HEADERS)) == _lib.CORE_HEADER == "dl4ss_hip.h"
+    assert list(_lib.HEADERS)[1:] == sorted(f for f in os.listdir(os.path.join(ROOT, "include"))
+                                            if f.endswith(".h") and f != "dl4ss_hip.h")
+    assert len(_lib.SIGNATURES) == sum(len(h.signatures) for h in _lib.HEADERS.values()) == 110
+    assert len(_lib.CONSTANTS) == sum(len(h.constants) for h in _lib.HEADERS.values()) == 35
+    assert _lib.exported_symbols() == list(_lib.SIGNATURES) == [n for h in _lib.HEADERS.values() for n in h.signatures]
+    for h in _lib.HEADERS.values():
+        assert isinstance(h, _lib.Header) and set(h.signatures) == set(h.restypes) == set(h.params)
+        for name in h.signatures:
+            assert (_lib.SIGNATURES[name], _lib.RESTYPES[name], _lib.PARAMS[name]) == \
+                (h.signatures[name], h.restypes[name], h.params[name]), name
+        assert h.constants.items() <= _lib.CONSTANTS.items()
+    assert set(_lib._SLOTS) == set(_lib.PARAMS) == set(_lib.RESTYPES) == set(_lib.SIGNATURES)
 
 
 def test_parameter_names_are_the_headers():
-    """PARAMS against a second, independent reading of the header (the one test_birnn_wrappers_cpu.py uses)."""
-    text = open(os.path.join(ROOT, "include", "dl4ss_hip.h")).read()
-    for name, params in _lib.PARAMS.items():
-        m = re.search(r"\b(?:int|long long|void)\s+" + name + r"\s*\(([^)]*)\)\s*;", text)
-        assert m, name
-        assert [re.split(r"[\s*]+", p.strip().split("[")[0])[-1] for p in m.group(1).split(",")] == list(params), name
-        assert len(set(params)) == len(params), name
+    """Each header's params against a second, independent reading of its file (the one test_birnn_wrappers_cpu.py
+    uses)."""
+    for header, (_, _, table, _) in _lib.HEADERS.items():
+        text = open(os.path.join(ROOT, "include", header)).read()
+        assert table, header
+        for name, params in table.items():
+            m = re.search(r"\b(?:int|long long|void)\s+" + name + r"\s*\(([^)]*)\)\s*;", text)
+            assert m, name
+            assert [re.split(r"[\s*]+", p.strip().split("[")[0])[-1] for p in m.group(1).split(",")] == list(params), \
+                name
+            assert len(set(params)) == len(params), name
 
 
 # ---- the parser fails closed ----
@@ -239,7 +264,9 @@ def test_bind_renames_the_python_keywords():
     assert _lib.bind("dl4ss_disc_adv_heads", ("s", 3), dict(lambda_=0.5, loss="l", dscore_dis="d", dscore_adv="a",
                                                              stream="st")) == ("s", 3, 0.5, "l", "d", "a", "st")
     renamed = {(e, p) for e, ps in _lib.PARAMS.items() for p in ps if p + "_" in _lib._SLOTS[e]}
-    assert {p for _, p in renamed} == {"pass", "lambda"} and len(renamed) == 5
+    core = {(e, p) for e, p in renamed if e in CORE.params}
+    assert {p for _, p in core} == {"pass", "lambda"} and len(core) == 5
+    assert renamed - core == {("dl4ss_mask_attn_align_loss_ex", "pass")}  # (of the other headers)
 
 
 # ---- a stubbed library: records what call / query hand it, touches nothing ----
@@ -312,13 +339,14 @@ RETIRED = ("DL4SS_ATTN_TILES", "DL4SS_RNN_MAX_WG", "DL4SS_RNN_MIN_BC")
 
 @pytest.fixture
 def unloaded(monkeypatch):
-    """_lib as before its first load, with ctypes.CDLL stubbed: _load() binds a stand-in, no shared object."""
+    """_lib as before its first load, with ctypes.CDLL stubbed: _load() binds a stand-in with the core header's names
+    alone, no shared object."""
     for name in RETIRED:
         monkeypatch.delenv(name, raising=False)
     monkeypatch.setattr(_lib, "_lib", None)
     monkeypatch.setattr(_lib, "LIB_PATH", __file__)  # (_load only asks whether the path exists: no built library)
     monkeypatch.setattr(_lib.ctypes, "CDLL", lambda path: types.SimpleNamespace(
-        hipGetErrorString=types.SimpleNamespace(), **{n: types.SimpleNamespace() for n in _lib.SIGNATURES}))
+        hipGetErrorString=types.SimpleNamespace(), **{n: types.SimpleNamespace() for n in CORE.signatures}))
 
 
 @pytest.mark.parametrize("name", RETIRED)

@@ -296,41 +296,45 @@ def test_check_settles_and_raises_on_the_sticky_bit(monkeypatch):
 
 # ---- the third header -----------------------------------------------------------------------------------------------
 ENTRIES = {"dl4ss_nadam", "dl4ss_adam_clipped_ex"}
+CORE, OPTIM = _lib.HEADERS["dl4ss_hip.h"], _lib.HEADERS["dl4ss_optim.h"]
 
 
 def test_optim_params_are_the_headers():
-    """OPTIM_PARAMS against a second, independent reading of the header."""
+    """The third header's params against a second, independent reading of the header."""
     text = open(os.path.join(ROOT, "include", "dl4ss_optim.h")).read()
-    assert set(_lib.OPTIM_PARAMS) == set(_lib.OPTIM_SIGNATURES) == ENTRIES == set(_lib.optim_exported_symbols())
-    for name, params in _lib.OPTIM_PARAMS.items():
+    assert set(OPTIM.params) == set(OPTIM.signatures) == ENTRIES == set(_lib.exported_symbols("dl4ss_optim.h"))
+    for name, params in OPTIM.params.items():
         m = re.search(r"\b(?:int|long long|void)\s+" + name + r"\s*\(([^)]*)\)\s*;", text)
         assert m, name
         assert [re.split(r"[\s*]+", p.strip().split("[")[0])[-1] for p in m.group(1).split(",")] == list(params), name
-        assert len(set(params)) == len(params) and len(_lib.OPTIM_SIGNATURES[name]) == len(params), name
-        assert _lib.OPTIM_RESTYPES[name] is I
+        assert len(set(params)) == len(params) and len(OPTIM.signatures[name]) == len(params), name
+        assert OPTIM.restypes[name] is I
     upd = [P, P, P, P, LL, F, F, F, F, I]
     tail = [P, P, F, P, I, P, P, P, P, P, P, I, I, F, P, P, I, P]
-    assert _lib.OPTIM_SIGNATURES["dl4ss_nadam"] == upd + [D, D, D] + tail
-    assert _lib.OPTIM_SIGNATURES["dl4ss_adam_clipped_ex"] == upd + tail
-    clipped = _lib.PARAMS["dl4ss_adam_clipped"]  # the _ex entry: dl4ss_adam_clipped plus clip_rule and the sticky flag
-    assert [p for p in _lib.OPTIM_PARAMS["dl4ss_adam_clipped_ex"] if p not in ("clip_rule", "nonfinite_sticky")] == \
+    assert OPTIM.signatures["dl4ss_nadam"] == upd + [D, D, D] + tail
+    assert OPTIM.signatures["dl4ss_adam_clipped_ex"] == upd + tail
+    clipped = CORE.params["dl4ss_adam_clipped"]  # the _ex entry: dl4ss_adam_clipped plus clip_rule and the sticky flag
+    assert [p for p in OPTIM.params["dl4ss_adam_clipped_ex"] if p not in ("clip_rule", "nonfinite_sticky")] == \
         list(clipped)
-    assert _lib.OPTIM_CONSTANTS == dict(DL4SS_CLIP_TORCH=0, DL4SS_CLIP_KERAS=1, DL4SS_CLIP_MAX_PARTS=4096,
-                                        DL4SS_STATUS_NONFINITE_GRAD=4)
+    assert OPTIM.constants == dict(DL4SS_CLIP_TORCH=0, DL4SS_CLIP_KERAS=1, DL4SS_CLIP_MAX_PARTS=4096,
+                                   DL4SS_STATUS_NONFINITE_GRAD=4)
     assert (ops.CLIP_TORCH, ops.CLIP_KERAS, ops.CLIP_MAX_PARTS, ops.STATUS_NONFINITE_GRAD) == (0, 1, 4096, 4)
 
 
 def test_first_two_headers_tables_are_untouched_and_the_library_exports_the_third():
-    assert not ENTRIES & (set(_lib.SIGNATURES) | set(_lib.IMGQ_SIGNATURES)) and len(_lib.SIGNATURES) == 98
-    assert not any(k in _lib.CONSTANTS or k in _lib.IMGQ_CONSTANTS for k in _lib.OPTIM_CONSTANTS)
+    imgq = _lib.HEADERS["dl4ss_imgq.h"]
+    assert not ENTRIES & (set(CORE.signatures) | set(imgq.signatures)) and len(CORE.signatures) == 98
+    assert not any(k in CORE.constants or k in imgq.constants for k in OPTIM.constants)
+    with open(os.path.join(ROOT, "include", "dl4ss_hip.h")) as f:
+        assert CORE == _lib.parse_header(f.read())
     lib = _lib.lib()
     for name in ENTRIES:
         fn = getattr(lib, name)
-        assert fn.argtypes == _lib.OPTIM_SIGNATURES[name] and fn.restype is I
+        assert fn.argtypes == OPTIM.signatures[name] and fn.restype is I
     with pytest.raises(TypeError, match="dl4ss_optim.h"):
         _lib.bind("dl4ss_nothing", (), {})
     with pytest.raises(TypeError, match="'nonfinite_sticky'"):
-        _lib.bind("dl4ss_nadam", (), {p: 0 for p in _lib.OPTIM_PARAMS["dl4ss_nadam"] if p != "nonfinite_sticky"})
+        _lib.bind("dl4ss_nadam", (), {p: 0 for p in OPTIM.params["dl4ss_nadam"] if p != "nonfinite_sticky"})
 
 
 def test_a_library_without_the_third_header_loads_and_a_call_names_the_symbol(monkeypatch):
@@ -342,19 +346,19 @@ def test_a_library_without_the_third_header_loads_and_a_call_names_the_symbol(mo
 
     monkeypatch.setattr(_lib, "_lib", None)
     monkeypatch.setattr(_lib.ctypes, "CDLL", lambda path: Old(
-        hipGetErrorString=types.SimpleNamespace(), **{n: types.SimpleNamespace() for n in _lib.SIGNATURES}))
+        hipGetErrorString=types.SimpleNamespace(), **{n: types.SimpleNamespace() for n in CORE.signatures}))
     lib = _lib._load()
     assert lib.dl4ss_attn_nblk.argtypes == [I, I]
     with pytest.raises(AttributeError, match="dl4ss_nadam"):
-        _lib.call("dl4ss_nadam", *([None] * len(_lib.OPTIM_PARAMS["dl4ss_nadam"])))
+        _lib.call("dl4ss_nadam", *([None] * len(OPTIM.params["dl4ss_nadam"])))
     monkeypatch.setattr(_lib, "_lib", None)  # (the next _load binds the real library again)
 
 
 # ---- the call sites ---------------------------------------------------------------------------------------------
 def check(fake, entry, want):
-    """test_lib_bind_cpu.check for the third header's tables."""
+    """test_lib_bind_cpu.check against the third header's tables."""
     (name, args), = fake.calls
-    params, sig = _lib.OPTIM_PARAMS[entry], _lib.OPTIM_SIGNATURES[entry]
+    params, sig = OPTIM.params[entry], OPTIM.signatures[entry]
     assert name == entry and len(args) == len(params) == len(sig)
     for p, a, kind in zip(params, args, sig):
         w = want[p]
@@ -445,7 +449,7 @@ def test_guarded_adam_picks_the_entry_point(fake, monkeypatch):
     for opt in opts:
         opt.step(grad)
         (name, args), = [c for c in fake.calls if c[0] not in ("dl4ss_grad_sumsq_parts", "dl4ss_grad_sumsq")]
-        kw = dict(zip(_lib._ALL_PARAMS[name], args))
+        kw = dict(zip(_lib.PARAMS[name], args))
         got.append((name, kw.get("clip_rule"), kw.get("n_part"), kw.get("nonfinite_sticky"), kw["step"]))
         fake.calls.clear()
     assert got == [("dl4ss_adam_guarded_dp_scaled", None, None, None, 1), ("dl4ss_adam_clipped", None, 2, None, 1),
@@ -453,7 +457,7 @@ def test_guarded_adam_picks_the_entry_point(fake, monkeypatch):
                    ("dl4ss_nadam", 1, 4, 1, 1)]
     opts[-1].step(grad, step=9, summed=True)  # a borrowed count, the sum already taken: one launch
     (name, args), = fake.calls
-    kw = dict(zip(_lib.OPTIM_PARAMS[name], args))
+    kw = dict(zip(OPTIM.params[name], args))
     assert (kw["step"], opts[-1].step_count) == (9, 1)
     assert (kw["mu"], kw["mu_next"], kw["mu_prod"]) == nr.schedule(9)
     assert kw["part"] == tag(shared)

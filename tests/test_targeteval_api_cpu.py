@@ -16,6 +16,7 @@ from dl4ss_amd.voiceprint import SpeakerMemory, VoiceprintNet
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 ENTRIES = {"dl4ss_bss_gain_ws_bytes", "dl4ss_bss_gain", "dl4ss_te_assemble"}
 N = 4000
+CORE, EVAL = _lib.HEADERS["dl4ss_hip.h"], _lib.HEADERS["dl4ss_eval.h"]
 
 
 def _net(**kw):
@@ -174,9 +175,8 @@ def test_prepare_background_is_numpys_arithmetic():
 def test_eval_header_parses_and_collides_with_no_other():
     with open(os.path.join(ROOT, "include", "dl4ss_eval.h")) as f:
         sigs, res, params, consts = _lib.parse_header(f.read(), "dl4ss_eval.h")
-    assert set(sigs) == ENTRIES == set(_lib.EVAL_SIGNATURES) == set(_lib.eval_exported_symbols())
-    assert (sigs, res, params, consts) == (_lib.EVAL_SIGNATURES, _lib.EVAL_RESTYPES, _lib.EVAL_PARAMS,
-                                           _lib.EVAL_CONSTANTS)
+    assert set(sigs) == ENTRIES == set(EVAL.signatures) == set(_lib.exported_symbols("dl4ss_eval.h"))
+    assert (sigs, res, params, consts) == EVAL
     P, I, LL = _lib.P, _lib.I, _lib.LL
     assert sigs["dl4ss_bss_gain"] == [P, P, P, P, I, I, I, I, P, LL, P, P, P]
     assert params["dl4ss_bss_gain"] == ("src", "est", "index", "n_eff", "M", "J", "Ke", "N", "ws", "ws_bytes", "crit",
@@ -186,21 +186,21 @@ def test_eval_header_parses_and_collides_with_no_other():
     assert res["dl4ss_bss_gain_ws_bytes"] is LL and res["dl4ss_bss_gain"] is I and res["dl4ss_te_assemble"] is I
     assert params["dl4ss_bss_gain"][-1] == params["dl4ss_te_assemble"][-1] == "stream"
     assert consts == {"DL4SS_BSS_GAIN_MAX_SRC": 4, "DL4SS_BSS_GAIN_CHUNK": 4096}
-    others = set(_lib.SIGNATURES) | set(_lib.IMGQ_SIGNATURES) | set(_lib.OPTIM_SIGNATURES)
-    assert not ENTRIES & others
-    assert not set(consts) & (set(_lib.CONSTANTS) | set(_lib.IMGQ_CONSTANTS) | set(_lib.OPTIM_CONSTANTS))
+    others = [h for name, h in _lib.HEADERS.items() if name != "dl4ss_eval.h"]
+    assert len(others) >= 3 and not ENTRIES & {n for h in others for n in h.signatures}
+    assert not set(consts) & {k for h in others for k in h.constants}
     # the first header's tables stay what dl4ss_hip.h declares
     with open(os.path.join(ROOT, "include", "dl4ss_hip.h")) as f:
-        first = _lib.parse_header(f.read())
-    assert first == (_lib.SIGNATURES, _lib.RESTYPES, _lib.PARAMS, _lib.CONSTANTS)
-    assert _lib.exported_symbols() == list(_lib.SIGNATURES) and not ENTRIES & set(_lib.exported_symbols())
+        assert CORE == _lib.parse_header(f.read())
+    assert _lib.exported_symbols("dl4ss_hip.h") == list(CORE.signatures)
+    assert not ENTRIES & set(_lib.exported_symbols("dl4ss_hip.h"))
 
 
 def test_the_library_exports_the_eval_entry_points_and_sizes_the_workspace():
     lib = _lib.lib()
     for name in ENTRIES:
         fn = getattr(lib, name)
-        assert fn.argtypes == _lib.EVAL_SIGNATURES[name] and fn.restype is _lib.EVAL_RESTYPES[name]
+        assert fn.argtypes == EVAL.signatures[name] and fn.restype is EVAL.restypes[name]
     nm = subprocess.run(["nm", "-D", "--defined-only", _lib.LIB_PATH], capture_output=True, text=True)
     if nm.returncode == 0:  # (binutils present) exactly the declared symbols of targeteval.hip are exported
         exported = {ln.split()[-1] for ln in nm.stdout.splitlines()
@@ -214,14 +214,31 @@ def test_the_library_exports_the_eval_entry_points_and_sizes_the_workspace():
 
 
 def test_a_header_that_declares_a_name_again_is_refused():
-    """the rule _lib applies to dl4ss_eval.h at import: a name of an earlier header may not come back"""
+    """the rule _lib applies to every header at import (merge_headers): neither an entry point nor a constant of an
+    earlier header may come back"""
     with open(os.path.join(ROOT, "include", "dl4ss_eval.h")) as f:
         text = f.read()
     again = text.replace("int dl4ss_te_assemble(", "int dl4ss_grad_sumsq(")
-    sigs = _lib.parse_header(again, "dl4ss_eval.h")[0]
-    assert set(sigs) & set(_lib.SIGNATURES) == {"dl4ss_grad_sumsq"}
-    src = open(_lib.__file__).read()
-    assert 'raise ValueError(f"dl4ss_eval.h declares again' in src
+    doctored = _lib.Header(*_lib.parse_header(again, "dl4ss_eval.h"))
+    assert set(doctored.signatures) & set(CORE.signatures) == {"dl4ss_grad_sumsq"}
+    with pytest.raises(ValueError) as e:
+        _lib.merge_headers({"dl4ss_hip.h": CORE, "dl4ss_eval.h": doctored})
+    assert all(word in str(e.value) for word in ("dl4ss_grad_sumsq", "dl4ss_eval.h", "dl4ss_hip.h"))
+    assert str(e.value).index("dl4ss_eval.h") < str(e.value).index("dl4ss_hip.h")  # the one that repeats, then the first
+    # a constant: a second header that defines DL4SS_CLIP_MAX_PARTS after dl4ss_optim.h has
+    optim = _lib.HEADERS["dl4ss_optim.h"]
+    assert "DL4SS_CLIP_MAX_PARTS" in optim.constants
+    redefines = _lib.Header(*_lib.parse_header(text + "\n#define DL4SS_CLIP_MAX_PARTS 8\n", "dl4ss_eval.h"))
+    assert redefines.signatures == EVAL.signatures and redefines.constants == dict(EVAL.constants, DL4SS_CLIP_MAX_PARTS=8)
+    with pytest.raises(ValueError) as e:
+        _lib.merge_headers({"dl4ss_hip.h": CORE, "dl4ss_optim.h": optim, "dl4ss_eval.h": redefines})
+    assert all(word in str(e.value) for word in ("DL4SS_CLIP_MAX_PARTS", "dl4ss_eval.h", "dl4ss_optim.h"))
+    assert "dl4ss_hip.h" not in str(e.value)
+    # the controls: the undoctored sets merge, into the tables _lib carries
+    merged = _lib.merge_headers({"dl4ss_hip.h": CORE, "dl4ss_optim.h": optim, "dl4ss_eval.h": EVAL})
+    assert len(merged.signatures) == 98 + 2 + 3 and merged.constants == {**CORE.constants, **optim.constants,
+                                                                         **EVAL.constants}
+    assert _lib.merge_headers(_lib.HEADERS) == (_lib.SIGNATURES, _lib.RESTYPES, _lib.PARAMS, _lib.CONSTANTS)
     with pytest.raises(TypeError, match="dl4ss_eval.h"):
         _lib.bind("dl4ss_bss_nothing", (), {})
 
