@@ -11,6 +11,7 @@ pure function of it, so a settled count needs no further state.  DESIGN.md secti
 import torch
 
 from . import _lib, ops
+from .params import check_tensor, mismatch
 
 
 def delegate(holder, name, default=None):
@@ -28,6 +29,19 @@ def timed_out_steps(refused, optimizers):
     that word.  Each update of a counted one counts a timed-out step; a non-finite refusal is counted once."""
     nonfinite = sum(opt.pending_nonfinite() for opt, _ in optimizers)
     return (refused - nonfinite) // sum(n for opt, n in optimizers if opt.counted)
+
+
+def require_settled(status, optimizers, what):
+    """Training state is read and written on a settled trainer only: raise RuntimeError, telling the caller to run
+    check() first, while the status word ``status`` is non-zero or one of ``optimizers`` has non-finite refusals
+    that settle() has not yet taken out of its step count.  Synchronises first (a device read)."""
+    if status.is_cuda:
+        torch.cuda.synchronize()
+    s = [int(x) for x in status.tolist()]
+    pending = sum(opt.pending_nonfinite() for opt in optimizers)
+    if any(s) or pending:
+        raise RuntimeError(f"{what}: the trainer is not settled (status {s}, {pending} non-finite refusal(s) "
+                           "pending): step_count still counts refused updates; run check() first")
 
 
 _SCHEDULE = {}  # the default cache: (beta1, schedule_decay) -> [step, mu(step), P(step)]
@@ -161,3 +175,43 @@ class GuardedAdam:
         self.step_count -= timed_out * updates_per_step + nonfinite
         self.skipped_nonfinite += nonfinite
         return nonfinite
+
+    # ---- training state (checkpoint.save_training_state)
+    def hyper(self):
+        """What a saved state is checked against, never restored: the update rule and its constants."""
+        return {"kind": self.kind, "betas": [float(b) for b in self.betas], "eps": float(self.eps),
+                "schedule_decay": self.schedule_decay,
+                "clip_norm": None if self.clip_norm is None else float(self.clip_norm),
+                "clipnorm": None if self.clipnorm is None else float(self.clipnorm)}
+
+    def state_dict(self):
+        """Host copies of m and v, the counts, lr (state: schedules assign it) and hyper().  Nadam's schedule is a
+        pure function of step_count (nadam_schedule) and is not saved.  Of a settled optimizer only
+        (require_settled): an unsettled step_count still counts refused updates."""
+        return {"m": self.m.detach().to("cpu", copy=True), "v": self.v.detach().to("cpu", copy=True),
+                "step_count": int(self.step_count), "skipped_nonfinite": int(self.skipped_nonfinite),
+                "lr": float(self.lr), **self.hyper()}
+
+    def check_state_dict(self, sd, where="optimizer"):
+        """Raise ValueError naming the first field of ``sd`` this optimizer cannot take; nothing is written."""
+        if not isinstance(sd, dict):
+            raise ValueError(f"{where}: no optimizer state in the file")
+        for k, own in self.hyper().items():
+            if k not in sd or sd[k] != own:
+                raise mismatch(f"{where}.{k}", sd.get(k), own)
+        check_tensor(sd.get("m"), self.m, f"{where}.m")
+        check_tensor(sd.get("v"), self.v, f"{where}.v")
+        for k in ("step_count", "skipped_nonfinite"):
+            if isinstance(sd.get(k), bool) or not isinstance(sd.get(k), int) or sd[k] < 0:
+                raise mismatch(f"{where}.{k}", sd.get(k), "a count >= 0")
+        if isinstance(sd.get("lr"), bool) or not isinstance(sd.get("lr"), (int, float)):
+            raise mismatch(f"{where}.lr", sd.get("lr"), "a number")
+
+    def load_state_dict(self, sd, checked=False):
+        """In place: m and v by copy_ into the existing buffers (a captured graph and every view stay valid), the
+        counts and lr assigned.  ``checked``: check_state_dict(sd) has passed already."""
+        if not checked:
+            self.check_state_dict(sd)
+        self.m.copy_(sd["m"])
+        self.v.copy_(sd["v"])
+        self.step_count, self.skipped_nonfinite, self.lr = sd["step_count"], sd["skipped_nonfinite"], float(sd["lr"])

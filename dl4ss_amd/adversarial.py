@@ -54,3 +54,20 @@ class AdvStep:
         (disc_adv_update) on grad_adv -- each a step of the one Adam state, clipped on its own gradient."""
         for i, g in enumerate((self.disc.grad_dis, self.disc.grad_adv)[:self.updates]):
             self.opt.step(g, gnorm=self.opt.grad_norm[i] if self.opt.clip_norm is not None else None)
+
+    # ---- training state (checkpoint.save_training_state; the trainer checks that it is settled)
+    def state_dict(self):
+        """The Discriminator's flat buffer with its layout, and its Adam (moments, both updates' one count, lr)."""
+        return {"net": self.disc.flat_state(), "opt": self.opt.state_dict()}
+
+    def check_state_dict(self, sd, where="adversary"):
+        if not isinstance(sd, dict):
+            raise ValueError(f"{where}: no adversary section in the file")
+        self.disc.check_flat_state(sd.get("net"), f"{where}.net")
+        self.opt.check_state_dict(sd.get("opt"), f"{where}.optimizer")
+
+    def load_state_dict(self, sd, checked=False):
+        if not checked:
+            self.check_state_dict(sd)
+        self.disc.load_flat_state(sd["net"])
+        self.opt.load_state_dict(sd["opt"], checked=True)

@@ -20,9 +20,16 @@ path; a file the safe loader refuses raises.  The flat parameter buffers of ``Se
 ``ClassifierNet`` carry the same names under a module prefix (``mix.``, ``emb.``, ``adj.``),
 so loading is a rename and a copy; ``save_reference_params`` writes the reference layout
 back (one file per module, legacy-compatible keys).
+
+Those files hold weights.  ``save_training_state`` / ``load_training_state`` (at the end of this module) hold a
+whole run -- weights, optimizer moments and counts, schedules, the host RNG streams -- so that a run stopped
+anywhere continues as the run that was never stopped ("Training state").
 """
 import os
+import random
+import tempfile
 
+import numpy as np
 import torch
 
 PREFIX = {"hidden3d": "mix.", "emblayer": "emb.", "adjlayer": "adj.", "attlayer": "att."}
@@ -287,7 +294,8 @@ def _weight_tensors(obj):
 def snapshot_weights(*objs):
     """Copies, on the tensors' own device, of the flat parameter buffers of the given nets / encoders / trainers and
     of ``SpeakerMemory.mem`` -- what the Keras trees' ``save_weights`` covers at a new lowest validation loss
-    (nnet.py:160-165).  Optimizer state is not part of it.  Give the result to ``restore_weights``."""
+    (nnet.py:160-165).  Optimizer state is not part of it (``save_training_state`` writes a whole run to a file).
+    Give the result to ``restore_weights``."""
     snap = []
     for obj in objs:
         for owner, t in _weight_tensors(obj):
@@ -302,3 +310,152 @@ def restore_weights(snap):
         t.copy_(saved)
         if owner is not None and hasattr(owner, "params_changed"):
             owner.params_changed()
+
+
+# --------------------------------------------------------------------------- training state: save and resume a run
+TRAINING_STATE_FORMAT = "dl4ss-training-state"
+TRAINING_STATE_VERSION = 1
+
+
+def _check_plain(x, where):
+    """The file holds tensors and plain containers of str, int, float, bool and None only (what
+    ``torch.load(weights_only=True)`` reads back without an allow-list): TypeError naming the first thing that is
+    not."""
+    if x is None or isinstance(x, (str, int, float, bool, torch.Tensor)):
+        return
+    if isinstance(x, dict):
+        for k, v in x.items():
+            if not isinstance(k, str):
+                raise TypeError(f"{where}: key {k!r} is not a str")
+            _check_plain(v, f"{where}.{k}")
+    elif isinstance(x, (list, tuple)):
+        for i, v in enumerate(x):
+            _check_plain(v, f"{where}[{i}]")
+    else:
+        raise TypeError(f"{where}: a {type(x).__name__} cannot go into a training-state file (tensors and plain "
+                        "containers of str, int, float, bool and None only)")
+
+
+def _rng_state():
+    """Python ``random``, NumPy's global generator and torch's CPU generator (what the compat loaders draw from),
+    the two Mersenne Twister key arrays as int64 tensors."""
+    ver, key, gauss = random.getstate()
+    name, nkey, pos, has_gauss, cached = np.random.get_state()
+    return {"python": {"version": int(ver), "key": torch.tensor(key, dtype=torch.int64), "gauss_next": gauss},
+            "numpy": {"name": str(name), "key": torch.from_numpy(nkey.astype(np.int64)), "pos": int(pos),
+                      "has_gauss": int(has_gauss), "cached_gaussian": float(cached)},
+            "torch": torch.get_rng_state().clone()}
+
+
+def _check_rng_state(sd, path):
+    own = _rng_state()
+    if not isinstance(sd, dict):
+        raise ValueError(f"{path}: rng: the file holds no generator states (saved with rng=False)")
+    for gen in ("python", "numpy"):
+        if not isinstance(sd.get(gen), dict):
+            raise ValueError(f"{path}: rng.{gen}: not in the file")
+        for k in ("version", "name"):
+            if k in own[gen] and sd[gen].get(k) != own[gen][k]:
+                raise ValueError(f"{path}: rng.{gen}.{k}: the file has {sd[gen].get(k)!r}, this process has "
+                                 f"{own[gen][k]!r}")
+        key = sd[gen].get("key")
+        if not isinstance(key, torch.Tensor) or key.dtype != torch.int64 or key.shape != own[gen]["key"].shape \
+                or int(key.min()) < 0 or int(key.max()) >= 2 ** 32:
+            raise ValueError(f"{path}: rng.{gen}.key: not a Mersenne Twister key of {own[gen]['key'].numel()} words")
+    g = sd["python"].get("gauss_next")
+    if g is not None and not isinstance(g, float):
+        raise ValueError(f"{path}: rng.python.gauss_next: {g!r} is neither None nor a float")
+    for k, types in (("pos", int), ("has_gauss", int), ("cached_gaussian", float)):
+        if not isinstance(sd["numpy"].get(k), types):
+            raise ValueError(f"{path}: rng.numpy.{k}: {sd['numpy'].get(k)!r} is not a {types.__name__}")
+    t = sd.get("torch")
+    if not isinstance(t, torch.Tensor) or t.dtype != torch.uint8 or t.shape != own["torch"].shape:
+        raise ValueError(f"{path}: rng.torch: not a CPU generator state of {own['torch'].numel()} bytes")
+
+
+def _set_rng_state(sd):
+    p, n = sd["python"], sd["numpy"]
+    random.setstate((p["version"], tuple(int(x) for x in p["key"].tolist()), p["gauss_next"]))
+    np.random.set_state((n["name"], n["key"].numpy().astype(np.uint32), n["pos"], n["has_gauss"], n["cached_gaussian"]))
+    torch.set_rng_state(sd["torch"])
+
+
+def save_training_state(path, trainer, schedule=None, stopper=None, rng=True, extra=None):
+    """Write everything a run needs to continue as if it had not stopped, into one file: ``trainer.state_dict()``
+    (a ``SepTrainer`` or ``ClassifierTrainer``: weights, optimizer moments, applied-update and skipped counts, lr,
+    and of the parts it has the Discriminator and its Adam or the query encoder, its optimizer and the speaker
+    memory), the states of ``schedule`` (``schedule.LRHalving``) and ``stopper`` (``schedule.EarlyStopping``), with
+    ``rng`` the host generators the ``compat`` loaders draw from (Python ``random``, NumPy's global one, torch's
+    CPU one) and ``extra``, the caller's own small dict of primitives (epoch, batch index, list position, paths of
+    best-epoch snapshots).
+
+    Batch size, ``precision``, ``mode``, eager or graph and world size are deliberately NOT part of the state: a
+    run may continue at another batch size or precision.  Data parallel: the state is the same on every rank (the
+    same all-reduced gradient, the same counts), so one rank saves and every rank loads that file; no broadcast.
+
+    The trainer must be settled: this synchronises, and raises RuntimeError (run ``check()`` first) while a status
+    word is non-zero or a non-finite refusal is pending -- step_count would still count refused updates.  The file
+    holds tensors and plain containers only and is written atomically: to a temporary name in ``path``'s directory,
+    flushed, then ``os.replace``; a save that fails leaves the previous file as it was and no temporary behind."""
+    payload = {"format": TRAINING_STATE_FORMAT, "version": TRAINING_STATE_VERSION, "trainer": trainer.state_dict(),
+               "schedule": None if schedule is None else schedule.state_dict(),
+               "stopper": None if stopper is None else stopper.state_dict(),
+               "rng": _rng_state() if rng else None, "extra": dict(extra) if extra else {}}
+    _check_plain(payload, "state")
+    d = os.path.dirname(os.path.abspath(path))
+    os.makedirs(d, exist_ok=True)
+    fd, tmp = tempfile.mkstemp(dir=d, prefix=os.path.basename(path) + ".", suffix=".tmp")
+    try:
+        with os.fdopen(fd, "wb") as f:
+            torch.save(payload, f)
+            f.flush()
+            os.fsync(f.fileno())
+        os.replace(tmp, path)
+    except BaseException:
+        if os.path.exists(tmp):
+            os.remove(tmp)
+        raise
+    return path
+
+
+def load_training_state(path, trainer, schedule=None, stopper=None, rng=True):
+    """Load a ``save_training_state`` file into ``trainer`` (and ``schedule``, ``stopper``, the host generators) in
+    place and return the saved ``extra`` dict.  Read with ``torch.load(..., weights_only=True)``: a file the safe
+    loader refuses raises.  Everything is validated before anything is written -- format, version, the nets'
+    layouts (parameter names and shapes in order, cell, gates, attention, crm, adjust), each optimizer's kind and
+    hyper-parameters, a part (adversary, voiceprint, image query) on one side only, the memory's shape, a
+    ``schedule`` / ``stopper`` / ``rng`` asked for that the file does not hold: ValueError naming the field and both
+    values, with every buffer, counter and generator as it was.  ``lr`` is state and is restored.  Batch size,
+    precision, mode, eager or graph and world size are not part of the state and may differ from the saving run's.
+    A ``schedule`` or ``stopper`` in the file that the caller does not pass is left unread.
+
+    The buffers are written by ``copy_``: a graph captured before the load stays valid and replays on the loaded
+    state, and the bf16 weight copies are converted again by the next step."""
+    sd = torch.load(path, map_location="cpu", weights_only=True)
+    if not isinstance(sd, dict) or sd.get("format") != TRAINING_STATE_FORMAT:
+        raise ValueError(f"{path}: format: the file has {sd.get('format') if isinstance(sd, dict) else None!r}, "
+                         f"expected {TRAINING_STATE_FORMAT!r}")
+    v = sd.get("version")
+    if isinstance(v, bool) or not isinstance(v, int) or not 1 <= v <= TRAINING_STATE_VERSION:
+        raise ValueError(f"{path}: version: the file has {v!r}, this code reads versions 1..{TRAINING_STATE_VERSION}")
+    try:
+        trainer.check_state_dict(sd.get("trainer"))
+        if schedule is not None:
+            schedule.check_state_dict(sd.get("schedule"))
+        if stopper is not None:
+            stopper.check_state_dict(sd.get("stopper"))
+    except ValueError as e:
+        raise ValueError(f"{path}: {e}") from None
+    if rng:
+        _check_rng_state(sd.get("rng"), path)
+    extra = sd.get("extra")
+    if not isinstance(extra, dict):
+        raise ValueError(f"{path}: extra: the file has {type(extra).__name__}, expected a dict")
+    trainer.load_state_dict(sd["trainer"], checked=True)
+    if schedule is not None:
+        schedule.load_state_dict(sd["schedule"], checked=True)
+    if stopper is not None:
+        stopper.load_state_dict(sd["stopper"], checked=True)
+    if rng:
+        _set_rng_state(sd["rng"])
+    return extra

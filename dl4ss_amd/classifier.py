@@ -86,6 +86,36 @@ class ClassifierTrainer:
     step_count = adam.delegate("opt", "step_count")
     skipped_nonfinite = adam.delegate("opt", "skipped_nonfinite")  # counted by check()
 
+    # ------------------------------------------------------------------ training state (as SepTrainer's)
+    def require_settled(self, what="state_dict()"):
+        """Synchronise; RuntimeError unless check() has settled every refused update (adam.require_settled)."""
+        adam.require_settled(self.status, [self.opt], what)
+
+    def state_dict(self):
+        """Host copies in plain containers of the net's flat buffer with its layout and of the optimizer (moments,
+        applied-update count, lr, skipped count); batch size and precision are not part of it.  Of a settled trainer
+        only (RuntimeError: run check() first).  DESIGN.md section 5, "Training state"."""
+        self.require_settled()
+        return {"net": self.net.flat_state(), "opt": self.opt.state_dict()}
+
+    def check_state_dict(self, sd):
+        """Everything that refuses a load, before anything is written: ValueError naming the field and both values."""
+        self.require_settled("load_state_dict()")
+        if not isinstance(sd, dict):
+            raise ValueError("trainer: no trainer state in the file")
+        extra = sorted(set(sd) - {"net", "opt"})
+        if extra:  # a SepTrainer's parts
+            raise ValueError(f"{extra[0]}: the file has it, a ClassifierTrainer has no such part")
+        self.net.check_flat_state(sd.get("net"), "net")
+        self.opt.check_state_dict(sd.get("opt"), "optimizer")
+
+    def load_state_dict(self, sd, checked=False):
+        """Load a state_dict() in place (copy_ into the existing buffers)."""
+        if not checked:
+            self.check_state_dict(sd)
+        self.net.load_flat_state(sd["net"])
+        self.opt.load_state_dict(sd["opt"], checked=True)
+
     # ------------------------------------------------------------------ features
     def features(self, raw=None, gains=None, feats=None):
         """raw (B, K, N) sources + gains (B, K) -> |STFT| of the mixtures (B, T, F); or precomputed

@@ -22,7 +22,7 @@ import torch
 from . import _lib, adam, dp, ops
 from .adversarial import AdvStep
 from .ops import CELLS, DEFER_BIAS, DGH_PAD8, DOUT_SLABS, WS_ZEROED, pad8  # noqa: F401 (re-exported)
-from .params import DiscNet, FlatParams, SepNet, _ngate  # noqa: F401 (re-exported)
+from .params import DiscNet, FlatParams, SepNet, _ngate, mismatch  # noqa: F401 (re-exported)
 from .plan import RETIRED_KNOBS, check_args, step_plan  # noqa: F401 (re-exported)
 from .imagequery import ImageQueryStep
 from .voiceprint import VoiceprintStep
@@ -268,6 +268,55 @@ class SepTrainer:
     skipped_nonfinite = adam.delegate("opt", "skipped_nonfinite")
     adv_step_count = adam.delegate("adv_opt", "step_count")
     adv_skipped_nonfinite = adam.delegate("adv_opt", "skipped_nonfinite", default=0)
+
+    # ------------------------------------------------------------------ training state
+    def _sections(self):
+        """The trainer's optional parts by their name in a saved state (None: this trainer has none)."""
+        return {"adversary": self.adv, "voiceprint": self.vp if self.vnet is not None else None,
+                "image_query": self.vp if self.inet is not None else None}
+
+    def require_settled(self, what="state_dict()"):
+        """Synchronise; RuntimeError unless check() has settled every refused update (adam.require_settled)."""
+        opts = [self.opt] + [s.opt for s in (self.adv, self.vp) if s is not None]
+        adam.require_settled(self.status, opts, what)
+
+    def state_dict(self):
+        """Everything a continued run needs, as host copies in plain containers: the net's flat buffer with its
+        layout, the optimizer (moments, applied-update count, lr, skipped count), and of the parts this trainer has
+        the Discriminator and its Adam, or the query encoder, its optimizer and the speaker memory.  Batch size,
+        precision, mode, eager or graph and world size are not part of it: a run may continue under others.  Of a
+        settled trainer only (RuntimeError: run check() first).  DESIGN.md section 5, "Training state"."""
+        self.require_settled()
+        sd = {"net": self.net.flat_state(), "opt": self.opt.state_dict()}
+        sd.update({name: part.state_dict() for name, part in self._sections().items() if part is not None})
+        return sd
+
+    def check_state_dict(self, sd):
+        """Everything that refuses a load, before anything is written: ValueError naming the field and both values
+        (layout, optimizer kind and hyper-parameters, a part on one side only, the memory's shape)."""
+        self.require_settled("load_state_dict()")
+        if not isinstance(sd, dict):
+            raise ValueError("trainer: no trainer state in the file")
+        self.net.check_flat_state(sd.get("net"), "net")
+        self.opt.check_state_dict(sd.get("opt"), "optimizer")
+        for name, part in self._sections().items():
+            if (part is None) != (name not in sd):
+                raise mismatch(name, "present" if name in sd else "absent", "absent" if part is None else "present")
+            if part is not None:
+                part.check_state_dict(sd[name], name)
+
+    def load_state_dict(self, sd, checked=False):
+        """Load a state_dict() in place: copy_ into the existing buffers, so a graph captured before stays valid and
+        replays on the loaded state; every net written declares the change and the bf16 weight copies are marked
+        stale (the next step, eager or replayed, converts them again)."""
+        if not checked:
+            self.check_state_dict(sd)
+        self.net.load_flat_state(sd["net"])
+        self.opt.load_state_dict(sd["opt"], checked=True)
+        for name, part in self._sections().items():
+            if part is not None:
+                part.load_state_dict(sd[name], checked=True)
+        self.params_changed()
 
     # ------------------------------------------------------------------ features
     def features(self, raw, gains, lengths=None):

@@ -68,6 +68,57 @@ class FlatParams:
     def state_dict(self):
         return {name: self.view(name).detach().clone() for name, _ in self.specs}
 
+    # ---- training state (checkpoint.save_training_state): the flat buffer as one tensor beside its layout
+    def layout(self):
+        """What the flat buffer's bits mean, in plain containers: the parameter names and shapes in order, and the
+        net's ``cell``, ``gates``, ``attention``, ``crm``, ``adjust`` (None where a net has no such setting)."""
+        fp = {"params": [[name, [int(d) for d in shape]] for name, shape in self.specs]}
+        fp.update({k: getattr(self, k, None) for k in LAYOUT_FIELDS})
+        return fp
+
+    def flat_state(self):
+        """{"flat": a host copy of the whole flat buffer, "layout": layout()}."""
+        return {"flat": self.flat.detach().to("cpu", copy=True), "layout": self.layout()}
+
+    def check_flat_state(self, sd, where):
+        """Raise ValueError naming the first field in which ``sd`` (a flat_state()) is not this net's; nothing is
+        written."""
+        if not isinstance(sd, dict) or not isinstance(sd.get("layout"), dict):
+            raise ValueError(f"{where}: no flat buffer with a layout in the file")
+        saved, own = sd["layout"], self.layout()
+        for k in LAYOUT_FIELDS:
+            if saved.get(k) != own[k]:
+                raise mismatch(f"{where}.layout.{k}", saved.get(k), own[k])
+        ps, po = [(n, tuple(s)) for n, s in saved.get("params", [])], [(n, tuple(s)) for n, s in own["params"]]
+        for i in range(max(len(ps), len(po))):
+            a, b = (ps[i] if i < len(ps) else None), (po[i] if i < len(po) else None)
+            if a != b:
+                raise mismatch(f"{where}.layout.params[{i}] (of {len(ps)} in the file, {len(po)} here)", a, b)
+        check_tensor(sd.get("flat"), self.flat, f"{where}.flat")
+
+    def load_flat_state(self, sd):
+        """Copy a checked flat_state() into the existing buffer and declare the change (params_changed, where the
+        net has it)."""
+        self.flat.copy_(sd["flat"])
+        if hasattr(self, "params_changed"):
+            self.params_changed()
+
+
+LAYOUT_FIELDS = ("cell", "gates", "attention", "crm", "adjust")
+
+
+def mismatch(field, saved, own):
+    """The ValueError of a training-state field that differs: its name and both values."""
+    return ValueError(f"{field}: the file has {saved!r}, this trainer has {own!r}")
+
+
+def check_tensor(t, like, field):
+    """``t`` must be a tensor of ``like``'s dtype and shape (a saved buffer against the one it is copied into)."""
+    if not isinstance(t, torch.Tensor):
+        raise mismatch(field, type(t).__name__, f"a {like.dtype} tensor of shape {tuple(like.shape)}")
+    if t.dtype != like.dtype or tuple(t.shape) != tuple(like.shape):
+        raise mismatch(field, f"{t.dtype} {tuple(t.shape)}", f"{like.dtype} {tuple(like.shape)}")
+
 
 class SepNet(FlatParams):
     """Trainable parameters of the mask network, flat fp32 with named views.  ``gates``: "logistic" (torch's

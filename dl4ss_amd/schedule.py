@@ -28,6 +28,18 @@ class LRHalving:
         trainer.lr = self.at_epoch_start(epoch_idx)
         return trainer.lr
 
+    def state_dict(self):
+        """``lr`` is the state; ``every``, ``floor``, ``enabled`` say which schedule it is and are checked on load."""
+        return {"lr": float(self.lr), "every": self.every, "floor": self.floor, "enabled": bool(self.enabled)}
+
+    def check_state_dict(self, sd, where="schedule"):
+        _check_fields(self, sd, where, ("every", "floor", "enabled"), {"lr": (int, float)})
+
+    def load_state_dict(self, sd, checked=False):
+        if not checked:
+            self.check_state_dict(sd)
+        self.lr = float(sd["lr"])
+
 
 def evalver(lr=2e-4):
     """EvalVer.py:570-575."""
@@ -48,6 +60,20 @@ def classifier(lr=1e-5):
 def crm_evalver(lr=2e-4):
     """cRM_EvalVer.py:627 (disabled in the reference)."""
     return LRHalving(lr, every=50, floor=5e-6, enabled=False)
+
+
+def _check_fields(obj, sd, where, fixed, state):
+    """ValueError naming the first of the ``fixed`` fields of ``sd`` that is not ``obj``'s, or of the ``state``
+    fields ({name: types}) that is missing or of another type; nothing is written."""
+    if not isinstance(sd, dict):
+        raise ValueError(f"{where}: not in the file")
+    for k in fixed:
+        if k not in sd or sd[k] != getattr(obj, k):
+            raise ValueError(f"{where}.{k}: the file has {sd.get(k)!r}, this object has {getattr(obj, k)!r}")
+    for k, types in state.items():
+        if not isinstance(sd.get(k), types) or (isinstance(sd[k], bool) and bool not in types):
+            want = " or ".join(t.__name__ for t in types)
+            raise ValueError(f"{where}.{k}: the file has {sd.get(k)!r}, expected {want}")
 
 
 class EarlyStopping:
@@ -76,3 +102,17 @@ class EarlyStopping:
                     (self.max_epoch is not None and epoch == self.max_epoch - 1):
                 self.stop = True
         return snapshot
+
+    def state_dict(self):
+        """``best_loss``, ``best_epoch``, ``stop`` are the state; ``start``, ``patience``, ``max_epoch`` are checked."""
+        return {"best_loss": float(self.best_loss), "best_epoch": int(self.best_epoch), "stop": bool(self.stop),
+                "start": self.start, "patience": self.patience, "max_epoch": self.max_epoch}
+
+    def check_state_dict(self, sd, where="stopper"):
+        _check_fields(self, sd, where, ("start", "patience", "max_epoch"),
+                      {"best_loss": (float,), "best_epoch": (int,), "stop": (bool,)})
+
+    def load_state_dict(self, sd, checked=False):
+        if not checked:
+            self.check_state_dict(sd)
+        self.best_loss, self.best_epoch, self.stop = sd["best_loss"], sd["best_epoch"], sd["stop"]

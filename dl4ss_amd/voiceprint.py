@@ -22,7 +22,7 @@ import torch
 
 from . import _lib, ops
 from .adam import GuardedAdam
-from .params import FlatParams, check_gates
+from .params import FlatParams, check_gates, check_tensor
 
 EPS = 2.220446049250313e-16  # np.spacing(1)
 
@@ -245,6 +245,29 @@ class MemoryQueryStep:
 
     def reset_workspaces(self):
         """After a timed-out hand-off: nothing to reset unless the encoder has recurrences."""
+
+    # ---- training state (checkpoint.save_training_state; the trainer checks that it is settled).  Both
+    # subclasses hold nothing beyond this: their buffers are rewritten by every step
+    def state_dict(self):
+        """The encoder net's flat buffer with its layout, its optimizer (stepped at the mask net's count: its own
+        step_count stays what it was) and the speaker memory's rows."""
+        return {"net": self.net.flat_state(), "opt": self.opt.state_dict(),
+                "memory": {"mem": self.memory.mem.detach().to("cpu", copy=True)}}
+
+    def check_state_dict(self, sd, where="query"):
+        if not isinstance(sd, dict):
+            raise ValueError(f"{where}: no query-encoder section in the file")
+        self.net.check_flat_state(sd.get("net"), f"{where}.net")
+        self.opt.check_state_dict(sd.get("opt"), f"{where}.optimizer")
+        mem = sd["memory"].get("mem") if isinstance(sd.get("memory"), dict) else None
+        check_tensor(mem, self.memory.mem, f"{where}.memory.mem")
+
+    def load_state_dict(self, sd, checked=False):
+        if not checked:
+            self.check_state_dict(sd)
+        self.net.load_flat_state(sd["net"])
+        self.opt.load_state_dict(sd["opt"], checked=True)
+        self.memory.mem.copy_(sd["memory"]["mem"])
 
 
 class VoiceprintStep(MemoryQueryStep):
