@@ -15,6 +15,12 @@ classify raises at import, with the offending text: it never guesses.
 ``lambda_`` for the two that are Python keywords); ``bind`` refuses a missing, unknown or repeated parameter and
 any argument count but the prototype's with ``TypeError``, before the library is touched.
 
+An extension is a directory: the headers of ``include/<name>/`` declare the C ABI of a library of its own,
+``libdl4ss_<name>.so`` (``build.py`` links it from ``csrc/<name>/``).  They are parsed the same way into
+``EXT_HEADERS`` (by file name), kept out of the merged tables above -- those stay what ``libdl4ss_hip.so`` exports --
+and ``call`` / ``query`` / ``bind`` / ``exported_symbols`` find their entry points and constants (``EXT_CONSTANTS``)
+there.  An extension may not declare a name that another header has.
+
 The product path has no CPU fallback: if the library is missing or a call returns a non-zero ``hipError_t`` this
 raises ``RuntimeError`` with the HIP error string.  Tensors are passed as raw device pointers; every call is
 enqueued on torch's current HIP stream.
@@ -104,7 +110,7 @@ def merge_headers(parsed):
 
 def _parse(name):
     with open(os.path.join(INCLUDE, name)) as f:
-        return Header(*parse_header(f.read(), name))
+        return Header(*parse_header(f.read(), os.path.basename(name)))
 
 
 HEADERS = {name: _parse(name) for name in
@@ -113,6 +119,30 @@ SIGNATURES, RESTYPES, PARAMS, CONSTANTS = merge_headers(HEADERS)
 # keyword -> slot of every entry point (a header name that is a Python keyword takes a trailing underscore)
 _SLOTS = {name: {p + "_" if keyword.iskeyword(p) else p: i for i, p in enumerate(ps)}
           for name, ps in PARAMS.items()}
+
+
+def _parse_extensions():
+    """(file name -> Header, file name -> library path) of the headers of include/<name>/, refusing a repeated file
+    name or a symbol that a header parsed before declares."""
+    headers, libs, first = {}, {}, {s: n for n, h in HEADERS.items() for s in (*h.signatures, *h.constants)}
+    for ext in sorted(d for d in os.listdir(INCLUDE) if os.path.isdir(os.path.join(INCLUDE, d))):
+        for f in sorted(f for f in os.listdir(os.path.join(INCLUDE, ext)) if f.endswith(".h")):
+            if f in HEADERS or f in headers:
+                raise ValueError(f"include/{ext}/{f}: a header of that name exists already")
+            headers[f] = _parse(os.path.join(ext, f))
+            libs[f] = os.path.join(_HERE, f"libdl4ss_{ext}.so")
+            for symbol in (*headers[f].signatures, *headers[f].constants):
+                if symbol in first:
+                    raise ValueError(f"{f} declares {symbol} again: {first[symbol]} has it")
+                first[symbol] = f
+    return headers, libs
+
+
+EXT_HEADERS, EXT_LIBS = _parse_extensions()
+EXT_CONSTANTS = {k: v for h in EXT_HEADERS.values() for k, v in h.constants.items()}
+_EXT_OF = {entry: name for name, h in EXT_HEADERS.items() for entry in h.signatures}  # entry point -> its header
+_EXT_SLOTS = {entry: {p + "_" if keyword.iskeyword(p) else p: i for i, p in enumerate(EXT_HEADERS[name].params[entry])}
+              for entry, name in _EXT_OF.items()}
 # knobs the library itself used to read from the environment, retired with plan.RETIRED_KNOBS
 RETIRED_ENV = ("DL4SS_ATTN_TILES", "DL4SS_RNN_MAX_WG", "DL4SS_RNN_MIN_BC")
 
@@ -153,9 +183,34 @@ def lib():
     return _load()
 
 
+_ext_libs = {}
+
+
+def _load_ext(header):
+    """The extension library that defines ``header``'s entry points, every one of them bound (all must resolve)."""
+    if header not in _ext_libs:
+        path = EXT_LIBS[header]
+        if not os.path.exists(path):
+            raise RuntimeError(f"dl4ss extension library not found at {path}; run `python -m dl4ss_amd.build` "
+                               "(there is no CPU fallback)")
+        ext, h = ctypes.CDLL(path), EXT_HEADERS[header]
+        for name, argtypes in h.signatures.items():
+            fn = getattr(ext, name)
+            fn.argtypes, fn.restype = argtypes, h.restypes[name]
+        _ext_libs[header] = ext
+    return _ext_libs[header]
+
+
+def _entry(name):
+    """The bound function ``name`` of the library that defines it."""
+    return getattr(_load_ext(_EXT_OF[name]) if name in _EXT_OF else _load(), name)
+
+
 def exported_symbols(header=None):
-    """Every declared entry point, or those of the one header (a file name) given."""
-    return list(SIGNATURES if header is None else HEADERS[header].signatures)
+    """Every entry point of libdl4ss_hip.so, or those of the one header (a file name, an extension's too) given."""
+    if header is None:
+        return list(SIGNATURES)
+    return list((HEADERS[header] if header in HEADERS else EXT_HEADERS[header]).signatures)
 
 
 def stream_ptr(stream=None):
@@ -179,12 +234,13 @@ def ptr(t, strided=False):
 def bind(name, args, kw):
     """The positional tuple of one call of ``name``: ``args`` first, then ``kw`` by the header's parameter names.
     ``TypeError`` unless every parameter of the prototype is given exactly once."""
-    slots = _SLOTS.get(name)
+    slots, params = (_EXT_SLOTS[name], EXT_HEADERS[_EXT_OF[name]].params[name]) if name in _EXT_OF else \
+        (_SLOTS.get(name), PARAMS.get(name))
     if slots is None:
         raise TypeError(f"{name} is not declared in " + ", ".join("include/" + h for h in HEADERS))
     n, given = len(slots), len(args) + len(kw)
     if len(args) > n:
-        raise TypeError(f"{name} takes {n} arguments (the last is {PARAMS[name][-1]!r}), {given} given")
+        raise TypeError(f"{name} takes {n} arguments (the last is {params[-1]!r}), {given} given")
     if not kw and given == n:
         return tuple(args)
     out = list(args) + [None] * (n - len(args))
@@ -204,14 +260,13 @@ def bind(name, args, kw):
 def query(name, *args, **kw):
     """Call an entry point that returns a value (sizes), not an error code."""
     args = bind(name, args, kw)
-    return getattr(_load(), name)(*args)
+    return _entry(name)(*args)
 
 
 def call(name, *args, **kw):
     args = bind(name, args, kw)
-    lb = _load()
-    rc = getattr(lb, name)(*args)
+    rc = _entry(name)(*args)
     if rc != 0:
-        msg = lb._hip.hipGetErrorString(rc).decode()
+        msg = _load()._hip.hipGetErrorString(rc).decode()
         raise RuntimeError(f"{name} failed: hipError {rc} ({msg})")
     return rc

@@ -9,6 +9,12 @@ entry points have a header of their own includes that one too, so a definition
 that disagrees with its prototype fails to compile.  Objects are rebuilt only
 when a source or header -- every public one included -- is newer than the
 object.
+
+An extension is a directory: the sources of ``csrc/<name>/*.hip`` are linked
+into a library of their own, ``libdl4ss_<name>.so``, whose C ABI is declared
+by the headers of ``include/<name>/`` (``_lib`` binds them from there).
+``libdl4ss_hip.so`` keeps exporting exactly what the headers directly under
+``include/`` declare.
 """
 import concurrent.futures as cf
 import os
@@ -46,14 +52,29 @@ def _compile(src, obj):
     return obj
 
 
-def build(verbose=False, jobs=None):
-    os.makedirs(OBJ, exist_ok=True)
-    srcs = sorted(f for f in os.listdir(CSRC) if f.endswith(".hip"))
-    headers = [os.path.join(d, f) for d in (CSRC, INCLUDE) for f in os.listdir(d) if f.endswith(".h")]
+def extensions():
+    """name -> source directory of every extension: the directories under csrc/ that hold .hip files."""
+    return {d: os.path.join(CSRC, d) for d in sorted(os.listdir(CSRC))
+            if d != "_obj" and os.path.isdir(os.path.join(CSRC, d))
+            and any(f.endswith(".hip") for f in os.listdir(os.path.join(CSRC, d)))}
+
+
+def ext_lib(name):
+    return os.path.join(HERE, f"libdl4ss_{name}.so")
+
+
+def _headers(ext=None):
+    dirs = [CSRC, INCLUDE] + ([os.path.join(CSRC, ext), os.path.join(INCLUDE, ext)] if ext else [])
+    return [os.path.join(d, f) for d in dirs if os.path.isdir(d) for f in os.listdir(d) if f.endswith(".h")]
+
+
+def _build_lib(src_dir, obj_dir, lib, headers, verbose, jobs):
+    os.makedirs(obj_dir, exist_ok=True)
+    srcs = sorted(f for f in os.listdir(src_dir) if f.endswith(".hip"))
     objs, todo = [], []
     for f in srcs:
-        src = os.path.join(CSRC, f)
-        obj = os.path.join(OBJ, f[:-4] + ".o")
+        src = os.path.join(src_dir, f)
+        obj = os.path.join(obj_dir, f[:-4] + ".o")
         objs.append(obj)
         if _newer(src, obj, headers):
             todo.append((src, obj))
@@ -62,11 +83,18 @@ def build(verbose=False, jobs=None):
         for obj in ex.map(lambda a: _compile(*a), todo):
             if verbose:
                 print("compiled", os.path.basename(obj), file=sys.stderr)
-    if todo or not os.path.exists(LIB) or any(os.path.getmtime(o) > os.path.getmtime(LIB) for o in objs):
-        cmd = [HIPCC, f"--offload-arch={ARCH}", "-shared", "-fPIC", *objs, "-o", LIB, *LINK]
+    if todo or not os.path.exists(lib) or any(os.path.getmtime(o) > os.path.getmtime(lib) for o in objs):
+        cmd = [HIPCC, f"--offload-arch={ARCH}", "-shared", "-fPIC", *objs, "-o", lib, *LINK]
         r = subprocess.run(cmd, capture_output=True, text=True)
         if r.returncode != 0:
             raise RuntimeError(f"link failed:\n{r.stderr}")
+    return lib
+
+
+def build(verbose=False, jobs=None):
+    _build_lib(CSRC, OBJ, LIB, _headers(), verbose, jobs)
+    for name, src_dir in extensions().items():
+        _build_lib(src_dir, os.path.join(OBJ, name), ext_lib(name), _headers(name), verbose, jobs)
     return LIB
 
 

@@ -74,6 +74,7 @@ class ClassifierTrainer:
         self.ws_bytes = ws
         self.rnn_ws = torch.zeros((ws + 7) // 8, device=dev, dtype=torch.int64)
         self.status = torch.zeros(2, device=dev, dtype=torch.int32)  # {hand-off timed out, refused updates}
+        self._feed = None  # corpus.CorpusFeed, made by the first features_corpus()
         cnet.grad = torch.zeros_like(cnet.flat)
         self.opt = adam.GuardedAdam(cnet.flat, self.status, self.loss, lr, betas, eps, clip_norm=self.clip_norm,
                                     kind=optimizer, schedule_decay=schedule_decay, clipnorm=self.clipnorm)
@@ -124,6 +125,17 @@ class ClassifierTrainer:
             self.feats.copy_(feats)
             return self.feats
         ops.mix_sources(raw, gains, out_src=self.src, out_mix=self.mix, stats_ws=self.stats)
+        ops.stft(self.mix, complex_out=False, mag_out=True, out_mag=self.feats)
+        return self.feats
+
+    def features_corpus(self, corpus, clips, gains, shifts=None):
+        """features() with the sources gathered from a device-resident corpus (corpus.DeviceCorpus) by clip id: host
+        arrays clips, gains, shifts (B, Ks), copied into trainer-owned device buffers, one mixing launch.  An
+        out-of-range clip id is a silent source, reported by check()."""
+        if self._feed is None:
+            from .corpus import CorpusFeed
+            self._feed = CorpusFeed(self.B, self.net.device)
+        self._feed.mix(corpus, clips, gains, shifts, self.K, self.N, self.src, self.mix)
         ops.stft(self.mix, complex_out=False, mag_out=True, out_mag=self.feats)
         return self.feats
 
@@ -219,3 +231,5 @@ class ClassifierTrainer:
             if s or timed_out:
                 self.rnn_ws.zero_()
                 raise RuntimeError(f"BiRNN hand-off timed out (status {s}): {timed_out} update(s) refused")
+        if self._feed is not None:
+            self._feed.check()

@@ -191,6 +191,7 @@ class SepTrainer:
         self.s2 = 0.0 if (mode == "crm" or loss_channels) else sum_weight / (B * T * F)
         self.spk = torch.empty(B, K, device=dev, dtype=torch.int32)
         self._works = []
+        self._feed = None  # corpus.CorpusFeed, made by the first corpus step
         self._in_chain = False
         self._side_stream = self._side_gemm = self._fork_ev = None
         self._wb_ver = None
@@ -321,6 +322,28 @@ class SepTrainer:
     # ------------------------------------------------------------------ features
     def features(self, raw, gains, lengths=None):
         ops.mix_sources(raw, gains, out_src=self.src, out_mix=self.mix, stats_ws=self.stats, lengths=lengths)
+        self._stfts()
+
+    def _mix_corpus(self, corpus, clips, gains, shifts, spk_idx=None):
+        """The step's sources and mixtures from a device-resident corpus (corpus.DeviceCorpus) in one launch: host
+        index arrays clips, gains, shifts (B, Ks), K <= Ks (a source behind the K targets is in the mixture only),
+        copied into trainer-owned device buffers in one asynchronous upload; spk_idx (B, K) goes with them when it is
+        a host array (a device tensor is copied as step() copies it).  An out-of-range clip id is a silent source,
+        reported by check()."""
+        if self._feed is None:
+            from .corpus import CorpusFeed  # (corpus imports the compat loaders' rules; not needed otherwise)
+            self._feed = CorpusFeed(self.B, self.net.device)
+        host_spk = None
+        if isinstance(spk_idx, torch.Tensor) and spk_idx.is_cuda:
+            self.spk.copy_(spk_idx)
+        elif spk_idx is not None:
+            host_spk = spk_idx.numpy() if isinstance(spk_idx, torch.Tensor) else spk_idx
+        self._feed.mix(corpus, clips, gains, shifts, self.K, self.N, self.src, self.mix, spk=host_spk,
+                       spk_out=self.spk)
+
+    def features_corpus(self, corpus, clips, gains, shifts=None):
+        """features() with the sources gathered from ``corpus`` by clip id instead of uploaded (``_mix_corpus``)."""
+        self._mix_corpus(corpus, clips, gains, shifts)
         self._stfts()
 
     def _stfts(self):
@@ -957,6 +980,19 @@ class SepTrainer:
         self.set_images(images)
         self.spk.copy_(spk_idx)
         self.features(raw, gains, lengths)
+        return self._step_tail()
+
+    def step_corpus(self, corpus, clips, gains, spk_idx, shifts=None, images=None):
+        """step() on a batch named by clip ids of a device-resident corpus: clips, gains, shifts host arrays
+        (B, Ks) (features_corpus); spk_idx (B, K) a device tensor or a host array (then it rides in the same upload:
+        nothing of the step waits for the device); everything behind the mixing launch is step()'s."""
+        self.set_images(images)
+        self._mix_corpus(corpus, clips, gains, shifts, spk_idx)
+        self._stfts()
+        return self._step_tail()
+
+    def _step_tail(self):
+        """step() behind its features: forward, loss, backward, all-reduce, update."""
         self.forward()
         loss = self.loss_and_grad()
         if self.buckets:
@@ -987,11 +1023,25 @@ class SepTrainer:
         An adversary is ignored: only the separation loss is reported.  Eager launches, also on a trainer that
         holds a captured graph.  A voiceprint= / image_query= trainer validates the target alone:
         targeteval.TargetEvaluator.eval_loss."""
+        self._eval_refusals()
+        self.spk.copy_(spk_idx)
+        self.features(raw, gains, lengths)
+        return self._eval_tail()
+
+    def eval_loss_corpus(self, corpus, clips, gains, spk_idx, shifts=None):
+        """eval_loss() on a batch named by clip ids of a device-resident corpus (features_corpus)."""
+        self._eval_refusals()
+        self._mix_corpus(corpus, clips, gains, shifts, spk_idx)
+        self._stfts()
+        return self._eval_tail()
+
+    def _eval_refusals(self):
         if self.vp is not None or self.vnet is not None or self.inet is not None:
             raise ValueError("eval_loss(): a voiceprint= / image_query= trainer is validated on the target alone, by "
                              "targeteval.TargetEvaluator.eval_loss")
-        self.spk.copy_(spk_idx)
-        self.features(raw, gains, lengths)
+
+    def _eval_tail(self):
+        """eval_loss() behind its features: forward, the attention COST pass, the loss."""
         self.forward()
         self.attn(0)
         st, perm = _lib.stream_ptr(), None
@@ -1075,6 +1125,19 @@ class SepTrainer:
         """step() with the captured graph: mixing, graph replay, all-reduce, Adam (bucketed: the
         early bucket's all-reduce between the first two replays, the middle one's between the second
         and the third)."""
+        self._graph_ready()
+        self.spk.copy_(spk_idx)
+        ops.mix_sources(raw, gains, out_src=self.src, out_mix=self.mix, stats_ws=self.stats)
+        return self._graph_tail()
+
+    def step_graph_corpus(self, corpus, clips, gains, spk_idx, shifts=None):
+        """step_corpus() with the captured graph: the one mixing launch stays an eager launch ahead of the replay,
+        so ragged lengths and shifts -- which step_graph() does not take -- run through the replayed step."""
+        self._graph_ready()
+        self._mix_corpus(corpus, clips, gains, shifts, spk_idx)
+        return self._graph_tail()
+
+    def _graph_ready(self):
         if self.vnet is not None:
             raise NotImplementedError("step_graph(): the voiceprint step is not built for HIP-graph capture; "
                                       "use step()")
@@ -1083,8 +1146,9 @@ class SepTrainer:
                                       "use step()")
         if getattr(self, "graph", None) is None:
             self.capture()
-        self.spk.copy_(spk_idx)
-        ops.mix_sources(raw, gains, out_src=self.src, out_mix=self.mix, stats_ws=self.stats)
+
+    def _graph_tail(self):
+        """step_graph() behind its mixing launch: replay, all-reduce, update."""
         if self.fast and self._wb_stale():
             # parameters changed outside Adam since the capture
             self._weights_to_bf16()
@@ -1125,6 +1189,11 @@ class SepTrainer:
         (bit 0) comes first whatever else is set, then bit 2 (also with bit 1 beside it: a step enqueued behind
         the refusal whose loss was not finite either), then bit 1."""
         torch.cuda.synchronize()
+        self._check_status()
+        if self._feed is not None:
+            self._feed.check()
+
+    def _check_status(self):
         s, refused = (int(x) for x in self.status.tolist())
         if s or refused:
             self.status.zero_()

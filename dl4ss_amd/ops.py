@@ -104,6 +104,96 @@ def mix_sources(raw, gains, out_src=None, out_mix=None, stats_ws=None, lengths=N
 
 
 # ---------------------------------------------------------------------------
+# device-resident corpus (include/corpus/dl4ss_corpus.h, libdl4ss_corpus.so; dl4ss_amd.corpus builds the pool)
+# ---------------------------------------------------------------------------
+CORPUS_DTYPES = {torch.int16: _lib.EXT_CONSTANTS["DL4SS_CORPUS_I16"],
+                 torch.float32: _lib.EXT_CONSTANTS["DL4SS_CORPUS_F32"]}
+MAX_MIX_SOURCES = 16  # K <= Ks <= 16, as dl4ss_mix_sources' K
+
+
+def _corpus_tables(name, pool, offsets, lengths):
+    """The pool and its tables as the kernels take them; -> n_clips."""
+    if not (pool.is_cuda and pool.dim() == 1 and pool.is_contiguous() and pool.dtype in CORPUS_DTYPES):
+        raise RuntimeError(f"{name}: pool must be a flat contiguous int16 or float32 CUDA tensor")
+    if pool.data_ptr() % 16:
+        raise RuntimeError(f"{name}: pool must be 16-B aligned")
+    n = offsets.numel()
+    for t, dt, what in ((offsets, torch.int64, "offsets"), (lengths, torch.int32, "lengths")):
+        if not (t.is_cuda and t.dtype == dt and t.is_contiguous() and tuple(t.shape) == (n,)):
+            raise RuntimeError(f"{name}: {what} must be a contiguous (n_clips,) {dt} CUDA tensor")
+    return n
+
+
+def corpus_stats(pool, offsets, lengths, out=None, ws=None):
+    """Per-clip {mean, 1 / max|x - mean|} (n_clips, 2) fp32 of a corpus pool, once per corpus: the statistics
+    mix_sources computes every step, with its arithmetic (dl4ss_corpus_stats)."""
+    n = _corpus_tables("corpus_stats", pool, offsets, lengths)
+    if out is None:
+        out = torch.empty(n, 2, device=pool.device, dtype=torch.float32)
+    if ws is None:
+        ws = torch.empty(max(1, 32 * n), device=pool.device, dtype=torch.float32)
+    _f32c(out, "corpus_stats(out)")
+    _f32c(ws, "corpus_stats(ws)")
+    if tuple(out.shape) != (n, 2) or ws.numel() < 32 * n:
+        raise RuntimeError("corpus_stats: out must be (n_clips, 2) and ws hold 32 n_clips floats")
+    _lib.call("dl4ss_corpus_stats", pool=_lib.ptr(pool), dtype=CORPUS_DTYPES[pool.dtype], offsets=_lib.ptr(offsets),
+              lengths=_lib.ptr(lengths), n_clips=n, ws=_lib.ptr(ws), clip_stats=_lib.ptr(out),
+              stream=_lib.stream_ptr())
+    return out
+
+
+def mix_corpus(pool, offsets, lengths, clip_stats, clips, gains, K, N, shifts=None, max_len=None, out_src=None,
+               out_mix=None, out_len=None, bad=None):
+    """One step's batch from a device-resident corpus in one launch (dl4ss_mix_corpus): clips, gains, shifts
+    (B, Ks) int32 / fp32 / int32 CUDA tensors name each source's clip, gain and rotation; sources 0..K-1 ->
+    out_src (B, K, N), all Ks summed -> out_mix (B, N), the values mix_sources gives for the gathered clips.
+    ``max_len``: the corpus's crop length; N below it is refused (the statistics are over the stored crop).
+    ``bad`` (1,) int32: goes up by one per source whose clip id is outside the corpus (that source is silent); a
+    fresh zeroed one unless given.  -> (out_src, out_mix, bad)."""
+    if max_len is not None and N < max_len:
+        raise ValueError(f"mix_corpus: N = {N} is below the corpus's max_len = {max_len} (the clip statistics are "
+                         "over the stored crop)")
+    n = _corpus_tables("mix_corpus", pool, offsets, lengths)
+    _f32c(clip_stats, "mix_corpus(clip_stats)")
+    _f32c(gains, "mix_corpus(gains)")
+    if tuple(clip_stats.shape) != (n, 2) or n < 1:
+        raise RuntimeError("mix_corpus: clip_stats must be (n_clips, 2), n_clips >= 1")
+    if clips.dim() != 2:
+        raise RuntimeError("mix_corpus: clips must be (B, Ks)")
+    B, Ks = clips.shape
+    if not (1 <= K <= Ks <= MAX_MIX_SOURCES) or N < 1 or B > 65535:
+        raise RuntimeError(f"mix_corpus: needs 1 <= K <= Ks <= {MAX_MIX_SOURCES}, N >= 1, B <= 65535 "
+                           f"(K {K}, Ks {Ks}, N {N}, B {B})")
+    for t, what in ((clips, "clips"), (shifts, "shifts")):
+        if t is not None and not (t.is_cuda and t.dtype == torch.int32 and t.is_contiguous()
+                                  and tuple(t.shape) == (B, Ks)):
+            raise RuntimeError(f"mix_corpus: {what} must be a contiguous (B, Ks) int32 CUDA tensor")
+    if tuple(gains.shape) != (B, Ks):
+        raise RuntimeError("mix_corpus: gains must be (B, Ks)")
+    dev = pool.device
+    if out_src is None:
+        out_src = torch.empty(B, K, N, device=dev, dtype=torch.float32)
+    if out_mix is None:
+        out_mix = torch.empty(B, N, device=dev, dtype=torch.float32)
+    if bad is None:
+        bad = torch.zeros(1, device=dev, dtype=torch.int32)
+    _f32c(out_src, "mix_corpus(out_src)")
+    _f32c(out_mix, "mix_corpus(out_mix)")
+    if tuple(out_src.shape) != (B, K, N) or tuple(out_mix.shape) != (B, N):
+        raise RuntimeError("mix_corpus: out_src must be (B, K, N) and out_mix (B, N)")
+    if out_len is not None and not (out_len.is_cuda and out_len.dtype == torch.int32 and out_len.is_contiguous()
+                                    and tuple(out_len.shape) == (B, Ks)):
+        raise RuntimeError("mix_corpus: out_len must be a contiguous (B, Ks) int32 CUDA tensor")
+    if not (bad.is_cuda and bad.dtype == torch.int32 and bad.numel() >= 1):
+        raise RuntimeError("mix_corpus: bad must be an int32 CUDA tensor")
+    _lib.call("dl4ss_mix_corpus", pool=_lib.ptr(pool), dtype=CORPUS_DTYPES[pool.dtype], offsets=_lib.ptr(offsets),
+              lengths=_lib.ptr(lengths), clip_stats=_lib.ptr(clip_stats), n_clips=n, clips=_lib.ptr(clips),
+              shifts=_lib.ptr(shifts), gains=_lib.ptr(gains), B=B, K=K, Ks=Ks, N=N, out_src=_lib.ptr(out_src),
+              out_mix=_lib.ptr(out_mix), out_len=_lib.ptr(out_len), bad=_lib.ptr(bad), stream=_lib.stream_ptr())
+    return out_src, out_mix, bad
+
+
+# ---------------------------------------------------------------------------
 # dense contractions
 # ---------------------------------------------------------------------------
 PREC = {"fp32": _C["DL4SS_PREC_F32"], "bf16": _C["DL4SS_PREC_BF16"]}
