@@ -20,25 +20,12 @@
 // order (bitwise deterministic).  PIT: the COST pass produces the K x K pairwise
 // cost matrix per utterance, `pit_select` picks the lowest-index minimising
 // permutation, the GRAD pass uses it; label order (the reference) = identity.
-#include "common.h"
+#include "attn_tile.h"
 #include <hip/hip_bf16.h>
 
 namespace {
 
-constexpr int NT = 256;
-constexpr int TILE = 256;  // rows per tile
-
-template <int K>
-struct Perms;
-template <>
-struct Perms<1> { static constexpr int N = 1; static constexpr int P[1][1] = {{0}}; };
-template <>
-struct Perms<2> { static constexpr int N = 2; static constexpr int P[2][2] = {{0, 1}, {1, 0}}; };
-template <>
-struct Perms<3> {
-  static constexpr int N = 6;
-  static constexpr int P[6][3] = {{0, 1, 2}, {0, 2, 1}, {1, 0, 2}, {1, 2, 0}, {2, 0, 1}, {2, 1, 0}};
-};
+using namespace attn_tile;
 
 struct AttnArgs {
   int B, T, F, rows_per_b, nblk;  // rows_per_b = T*F ; nblk = blocks per utterance
@@ -58,22 +45,243 @@ struct AttnArgs {
   float* part_dq;                 // (B, nblk, K, QW)
   float* mask_out;                // optional (B, K, T*F) [cRM: x2]
   float* pred_out;                // optional (B, K, T*F) [cRM: x2]
+  const float* gext;              // ADV: (B, K, T*F) gradient at the prediction, pred_out's layout; else null
 };
 
-// ADV (the adversarial step): the GRAD pass adds a second gradient at the prediction pred = mask |X|,
-// gext (B, K, T*F) in pred_out's layout (the Discriminator's conv1 dX): dm = (2 s1 (m x - y) + gext) x +
-// 2 s2 ds.  A compile-time form: the kernels without it are the same code as before.
-template <int E, int K, bool CRM, bool GRAD, bool VB>
+// One lane per (b,t,f) row.  ADV (the adversarial step): the GRAD pass adds a second gradient at the prediction
+// pred = mask |X|, a.gext (the Discriminator's conv1 dX): dm = (2 s1 (m x - y) + gext) x + 2 s2 ds.  A
+// compile-time form, instantiated with !CRM && GRAD only: the kernels without it carry no test of it.
+template <int E, int K, bool CRM, bool GRAD, bool VB, bool ADV = false>
 __global__ __launch_bounds__(NT) void attn_kernel(AttnArgs a) {
-  constexpr bool ADV = false;
-  const float* const gext = nullptr;
-#include "attn_kernel_body.h"
-}
+  constexpr int QW = CRM ? 2 * E : E;
+  constexpr int NC = CRM ? 2 : 1;  // components per bin
+  __shared__ __attribute__((aligned(16))) float sv[TILE * E];
+  __shared__ float sq[K * QW];
 
-template <int E, int K, bool VB>
-__global__ __launch_bounds__(NT) void attn_adv_kernel(AttnArgs a, const float* __restrict__ gext) {
-  constexpr bool CRM = false, GRAD = true, ADV = true;
-#include "attn_kernel_body.h"
+  const int b = blockIdx.y;
+  const int tid = threadIdx.x;
+  for (int i = tid; i < K * QW; i += NT) sq[i] = a.q[(long long)b * K * QW + i];
+
+  const auto [rbeg, rend] = block_rows(a.rows_per_b, a.nblk);
+  int pm[K];
+  load_perm(a.perm, b, pm);
+
+  float cost[K * K + 1];
+#pragma unroll
+  for (int i = 0; i < K * K + 1; ++i) cost[i] = 0.f;
+  __shared__ float sdl[GRAD ? TILE * K * NC : 1];  // dL/dlogit per tile row
+  float dqa[2] = {0.f, 0.f};  // dq[j] for j = tid, tid + 256 (j < K*QW)
+  const float* Vb = a.V + (long long)b * a.rows_per_b * E;
+  float* Db = (GRAD && a.dPre) ? a.dPre + (long long)b * a.rows_per_b * E : nullptr;
+
+  for (int r0 = rbeg; r0 < rend; r0 += TILE) {
+    const int nr = min(TILE, rend - r0);
+    __syncthreads();  // previous tile fully consumed (and sq visible on first pass)
+    // coalesced stage of nr rows (nr*E floats, 16-B aligned when r0*E*4 % 16 == 0); bf16 V:
+    // 4-B pairs (E even), widened to fp32 in LDS
+    if constexpr (VB) {
+      const unsigned* src = reinterpret_cast<const unsigned*>(a.Vb + ((long long)b * a.rows_per_b + r0) * E);
+      const int n2 = nr * E / 2;
+      // every load of the tile issued before the first LDS store (a load -> store loop
+      // kept one 4-B load per thread in flight)
+      constexpr int NW = (TILE * E / 2 + NT - 1) / NT;
+      unsigned w[NW];
+#pragma unroll
+      for (int q = 0; q < NW; ++q) {
+        const int i = tid + q * NT;
+        w[q] = i < n2 ? src[i] : 0u;
+      }
+#pragma unroll
+      for (int q = 0; q < NW; ++q) {
+        const int i = tid + q * NT;
+        if (i < n2)
+          reinterpret_cast<float2*>(sv)[i] = make_float2(__uint_as_float(w[q] << 16), __uint_as_float(w[q] & 0xFFFF0000u));
+      }
+    } else {
+      copy_f32(sv, Vb + (long long)r0 * E, nr * E, (((long long)r0 * E) & 3) == 0);
+    }
+    __syncthreads();
+    const int r = tid;
+    if (r < nr) {
+      const int row = r0 + r;
+      const float* v = sv + r * E;
+      float lg[K][NC];
+#pragma unroll
+      for (int k = 0; k < K; ++k)
+#pragma unroll
+        for (int c = 0; c < NC; ++c) lg[k][c] = 0.f;
+#pragma unroll
+      for (int e = 0; e < E; e += 2) {
+        const float2 vv = *reinterpret_cast<const float2*>(v + e);
+#pragma unroll
+        for (int k = 0; k < K; ++k)
+#pragma unroll
+          for (int c = 0; c < NC; ++c) {
+            lg[k][c] = fmaf(vv.x, sq[k * QW + c * E + e], lg[k][c]);
+            lg[k][c] = fmaf(vv.y, sq[k * QW + c * E + e + 1], lg[k][c]);
+          }
+      }
+      float dl[K][NC];  // dL/dlogit
+      if constexpr (!CRM) {
+        const float x = a.X[(long long)b * a.xs + row];
+        float m[K], y[K], msum = 0.f;
+#pragma unroll
+        for (int k = 0; k < K; ++k) {
+          m[k] = sigmoidf_(lg[k][0]);
+          msum += m[k];
+          y[k] = a.Y[(long long)b * a.ys + (long long)k * a.yks + row];
+        }
+#pragma unroll
+        for (int k = 0; k < K; ++k)
+#pragma unroll
+          for (int j = 0; j < K; ++j) {
+            const float dd = m[k] * x - y[j];
+            cost[k * K + j] = fmaf(dd, dd, cost[k * K + j]);
+          }
+        const float ds = msum - 1.0f;
+        cost[K * K] = fmaf(ds, ds, cost[K * K]);
+        if (a.mask_out || a.pred_out) {
+#pragma unroll
+          for (int k = 0; k < K; ++k) {
+            const long long o = ((long long)b * K + k) * a.rows_per_b + row;
+            if (a.mask_out) a.mask_out[o] = m[k];
+            if (a.pred_out) a.pred_out[o] = m[k] * x;
+          }
+        }
+        if constexpr (GRAD) {
+#pragma unroll
+          for (int k = 0; k < K; ++k) {
+            float yp = y[0], ge = 0.f;
+#pragma unroll
+            for (int j = 1; j < K; ++j) yp = pm[k] == j ? y[j] : yp;
+            if constexpr (ADV) ge = a.gext[((long long)b * K + k) * a.rows_per_b + row];
+            dl[k][0] = mag_dl<ADV>(a, k, m, x, yp, ds, ge);
+          }
+        }
+      } else {
+        const float2 x = *reinterpret_cast<const float2*>(a.X + 2 * ((long long)b * a.xs + row));
+        float2 p[K], y[K];
+#pragma unroll
+        for (int k = 0; k < K; ++k) {
+          // cRM_EvalVer.py:269 (10 tanh) and :688 (inverse compression), fp32 as the reference
+          const float mcr = 10.f * tanhf(lg[k][0]);
+          const float mci = 10.f * tanhf(lg[k][1]);
+          const float mr = -10.f * logf((10.f - mcr) / (10.f + mcr));
+          const float mi = -10.f * logf((10.f - mci) / (10.f + mci));
+          p[k] = make_float2(mr * x.x - mi * x.y, mr * x.y + mi * x.x);
+          y[k] = *reinterpret_cast<const float2*>(a.Y + 2 * ((long long)b * a.ys + (long long)k * a.yks + row));
+          if (a.mask_out) {
+            const long long o = 2 * (((long long)b * K + k) * a.rows_per_b + row);
+            a.mask_out[o] = mr;
+            a.mask_out[o + 1] = mi;
+          }
+          if (a.pred_out) {
+            const long long o = 2 * (((long long)b * K + k) * a.rows_per_b + row);
+            a.pred_out[o] = p[k].x;
+            a.pred_out[o + 1] = p[k].y;
+          }
+          if constexpr (GRAD) {
+            // d(M)/d(logit) through the same fp32 chain: dM/dMc * dMc/dl
+            const float dmc_r = 10.f * (1.f / (10.f - mcr) + 1.f / (10.f + mcr));
+            const float dmc_i = 10.f * (1.f / (10.f - mci) + 1.f / (10.f + mci));
+            dl[k][0] = dmc_r * (10.f * (1.f - (mcr * 0.1f) * (mcr * 0.1f)));
+            dl[k][1] = dmc_i * (10.f * (1.f - (mci * 0.1f) * (mci * 0.1f)));
+          }
+        }
+#pragma unroll
+        for (int k = 0; k < K; ++k)
+#pragma unroll
+          for (int j = 0; j < K; ++j) {
+            const float dr = p[k].x - y[j].x, di = p[k].y - y[j].y;
+            cost[k * K + j] = fmaf(dr, dr, fmaf(di, di, cost[k * K + j]));
+          }
+        if constexpr (GRAD) {
+#pragma unroll
+          for (int k = 0; k < K; ++k) {
+            float2 yp = y[0];
+#pragma unroll
+            for (int j = 1; j < K; ++j) yp = pm[k] == j ? y[j] : yp;
+            const float gr = 2.f * a.s1 * (p[k].x - yp.x), gi = 2.f * a.s1 * (p[k].y - yp.y);
+            // P = M (x) X: dMr = gr xr + gi xi ; dMi = -gr xi + gi xr
+            const float dmr = gr * x.x + gi * x.y;
+            const float dmi = -gr * x.y + gi * x.x;
+            dl[k][0] *= dmr;
+            dl[k][1] *= dmi;
+          }
+        }
+      }
+      if constexpr (GRAD) {
+#pragma unroll
+        for (int k = 0; k < K; ++k)
+#pragma unroll
+          for (int c = 0; c < NC; ++c) sdl[r * K * NC + k * NC + c] = dl[k][c];
+      }
+    } else if (GRAD) {
+#pragma unroll
+      for (int i = 0; i < K * NC; ++i) sdl[r * K * NC + i] = 0.f;
+    }
+    if constexpr (GRAD) {
+      __syncthreads();
+      // dq[k][c*E+e] += sum_r dl[r][k*NC+c] V[r][e]   (lanes along e: conflict-free)
+#pragma unroll
+      for (int h = 0; h < 2; ++h) {
+        const int j = tid + NT * h;
+        if (j < K * QW) {
+          const int k = j / QW, ce = j % QW, c = ce / E, e = ce % E;
+          float acc = 0.f;
+          for (int rr = 0; rr < nr; ++rr) acc = fmaf(sdl[rr * K * NC + k * NC + c], sv[rr * E + e], acc);
+          dqa[h] += acc;
+        }
+      }
+      __syncthreads();
+      // dV[e] = sum_k dl_k q_k[e] ; dPre = dV (1 - V^2), written in place over the own row
+      if (r < nr) {
+        float* v = sv + r * E;
+        float dl[K * NC];
+#pragma unroll
+        for (int i = 0; i < K * NC; ++i) dl[i] = sdl[r * K * NC + i];
+#pragma unroll
+        for (int e = 0; e < E; e += 2) {
+          const float2 vv = *reinterpret_cast<const float2*>(v + e);
+          float g0 = 0.f, g1 = 0.f;
+#pragma unroll
+          for (int k = 0; k < K; ++k)
+#pragma unroll
+            for (int c = 0; c < NC; ++c) {
+              const float d = dl[k * NC + c];
+              g0 = fmaf(d, sq[k * QW + c * E + e], g0);
+              g1 = fmaf(d, sq[k * QW + c * E + e + 1], g1);
+            }
+          *reinterpret_cast<float2*>(v + e) = make_float2(g0 * (1.f - vv.x * vv.x), g1 * (1.f - vv.y * vv.y));
+        }
+      }
+    }
+    if (GRAD && a.dPreB) {
+      // bf16 dPre for the Linear's backward GEMMs: pairs (e, e+1) as one 4-B store into
+      // row (b*T + t) of the padded bf16 matrix (E, F*E offsets and ldpb are even)
+      __syncthreads();
+      for (int i = tid; i < nr * E / 2; i += NT) {
+        const int rl = (2 * i) / E, e = (2 * i) % E;
+        const int row = r0 + rl;
+        const int t = row / a.F, f = row - t * a.F;
+        __hip_bfloat162 v2 = __float22bfloat162_rn(make_float2(sv[2 * i], sv[2 * i + 1]));
+        a.dPreB[(((long long)b * a.T + t) * a.ldpb + (long long)f * E + e) >> 1] = *reinterpret_cast<unsigned*>(&v2);
+      }
+    } else if constexpr (GRAD) {
+      __syncthreads();
+      copy_f32(Db + (long long)r0 * E, sv, nr * E, (((long long)r0 * E) & 3) == 0);
+    }
+  }
+
+  // ---- block reductions (fixed order: wave shuffle, then waves 0..3)
+  __syncthreads();
+  reduce_costs(cost, true, a.part_loss + ((long long)b * a.nblk + blockIdx.x) * (K * K + 1));
+  if constexpr (GRAD) {
+    float* pd = a.part_dq + ((long long)b * a.nblk + blockIdx.x) * K * QW;
+#pragma unroll
+    for (int h = 0; h < 2; ++h)
+      if (tid + NT * h < K * QW) pd[tid + NT * h] = dqa[h];
+  }
 }
 
 // The bf16-V magnitude path (the throughput step), one QUAD of lanes per (b,t,f) row.
@@ -105,23 +313,291 @@ __device__ __attribute__((aligned(16))) const unsigned g_attn_zero[4] = {0u, 0u,
 // image (sdp) for the same copy-out; everything else -- the quad's arithmetic and summation order,
 // the bf16 dPre, dq -- as in the bf16-V form.  The generic attn_kernel ran this step at ~2 TB/s
 // (C4 bf16s: 156 us per step for its one GRAD launch).
-template <int E, int K, bool GRAD, bool VF = false, bool CRM = false>
-__global__ __launch_bounds__(NT, (K == 3 && GRAD) || VF || CRM ? 2 : 4) void attn_q4_kernel(AttnArgs a) {
-  static_assert(E % 2 == 0, "bf16 pairs");
-  constexpr bool ADV = false;
-  const float* const gext = nullptr;
-#include "attn_q4_body.h"
-}
-
-// the adversarial GRAD pass on the quad layout: bf16 V (VF false) or fp32 V with bf16 dPre (VF true).
+// CRM (round 5): the complex-ratio-mask path (cRM_EvalVer.py:259-271, 688, 720-743) -- each row
+// has NC = 2 logits per query (the re / im halves of the 2E-wide query), the inverse-compressed mask
+// M, the complex prediction P = M (x) X and its squared error, as attn_kernel computes them (the same
+// fp32 tanhf / logf chain) -- on the quad layout; only the logits' summation order differs.
+// ADV: the adversarial GRAD pass (a.gext), on bf16 V or on fp32 V with bf16 dPre; !CRM && GRAD only.
 // K = 2 on bf16 V: the RPQ x K prefetched gext values do not fit the 128 VGPRs of 4 workgroups per CU
 // (28 B of scratch per lane); at 3 per CU (168 VGPRs) nothing spills
-template <int E, int K, bool VF>
-__global__ __launch_bounds__(NT, K == 3 || VF ? 2 : K == 2 ? 3 : 4) void attn_q4_adv_kernel(
-    AttnArgs a, const float* __restrict__ gext) {
+template <int E, int K, bool GRAD, bool VF = false, bool CRM = false, bool ADV = false>
+__global__ __launch_bounds__(NT, (K == 3 && GRAD) || VF || CRM ? 2 : (ADV && K == 2) ? 3 : 4) void attn_q4_kernel(
+    AttnArgs a) {
   static_assert(E % 2 == 0, "bf16 pairs");
-  constexpr bool GRAD = true, CRM = false, ADV = true;
-#include "attn_q4_body.h"
+  constexpr int NC = CRM ? 2 : 1;        // logits per (row, query)
+  constexpr int QW = NC * E;             // query width
+  constexpr int EP = E / 2;              // bf16 pairs per row
+  constexpr int NWL = (EP + 3) / 4;      // pairs per lane
+  constexpr int NQ = NT / 4;             // quads per block
+  constexpr int RPQ = TILE / NQ;         // rows per quad per tile
+  constexpr int WPR = VF ? E : EP;       // 4-B words of V per row
+  constexpr int NCH = (TILE * WPR + 3) / 4 + 1;  // 16-B chunks of a tile, misaligned start included
+  constexpr int NCHP = (NCH + 63) / 64 * 64;     // whole 1-KB DMA instructions
+  __shared__ __attribute__((aligned(16))) unsigned sv[NCHP * 4];
+  __shared__ __attribute__((aligned(16))) unsigned sdp[VF && GRAD ? TILE * EP : 1];
+  __shared__ float sdq[GRAD ? NT / 64 * K * QW : 1];
+
+  const int b = blockIdx.y;
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int j = tid & 3, qd = tid >> 2;
+  // this lane's q values (zero for the pair slots past EP)
+  float qv[K][NC][NWL][2];
+#pragma unroll
+  for (int k = 0; k < K; ++k)
+#pragma unroll
+    for (int c = 0; c < NC; ++c)
+#pragma unroll
+      for (int i = 0; i < NWL; ++i) {
+        const int w = j + 4 * i;
+        const float* qk = a.q + ((long long)b * K + k) * QW + c * E;
+        qv[k][c][i][0] = w < EP ? qk[2 * w] : 0.f;
+        qv[k][c][i][1] = w < EP ? qk[2 * w + 1] : 0.f;
+      }
+  const auto [rbeg, rend] = block_rows(a.rows_per_b, a.nblk);
+  int pm[K];
+  load_perm(a.perm, b, pm);
+  float cost[K * K + 1];
+#pragma unroll
+  for (int i = 0; i < K * K + 1; ++i) cost[i] = 0.f;
+  float dq[GRAD ? K : 1][GRAD ? NC : 1][GRAD ? NWL : 1][2];
+  if constexpr (GRAD) {
+#pragma unroll
+    for (int k = 0; k < K; ++k)
+#pragma unroll
+      for (int c = 0; c < NC; ++c)
+#pragma unroll
+        for (int i = 0; i < NWL; ++i) dq[k][c][i][0] = dq[k][c][i][1] = 0.f;
+  }
+  const unsigned* Vw = VF ? reinterpret_cast<const unsigned*>(a.V) : reinterpret_cast<const unsigned*>(a.Vb);
+  const long long totw = (long long)a.B * a.rows_per_b * WPR;
+
+  for (int r0 = rbeg; r0 < rend; r0 += TILE) {
+    const int nr = min(TILE, rend - r0);
+    // issue this tile's loads: X and the targets of the quad's rows (cRM: [re, im]), then V by 16-B chunks
+    float xr[RPQ][NC], yr[RPQ][K][NC];
+#pragma unroll
+    for (int s = 0; s < RPQ; ++s) {
+      const int r = qd + NQ * s;
+      const int row = r0 + (r < nr ? r : 0);
+#pragma unroll
+      for (int c = 0; c < NC; ++c) xr[s][c] = a.X[((long long)b * a.xs + row) * NC + c];
+#pragma unroll
+      for (int k = 0; k < K; ++k)
+#pragma unroll
+        for (int c = 0; c < NC; ++c) yr[s][k][c] = a.Y[((long long)b * a.ys + (long long)k * a.yks + row) * NC + c];
+    }
+    float ge[ADV ? RPQ : 1][ADV ? K : 1];  // ADV: the rows' gradient at the prediction, loaded with X and Y
+    if constexpr (ADV) {
+#pragma unroll
+      for (int s = 0; s < RPQ; ++s) {
+        const int r = qd + NQ * s;
+        const int row = r0 + (r < nr ? r : 0);
+#pragma unroll
+        for (int k = 0; k < K; ++k) ge[s][k] = a.gext[((long long)b * K + k) * a.rows_per_b + row];
+      }
+    }
+    const long long w0 = ((long long)b * a.rows_per_b + r0) * WPR;
+    const int off = (int)(w0 & 3);  // (VF: even -- E is -- so every pair is an aligned float2)
+    const long long wa = w0 - off;
+    const int nch = (off + nr * WPR + 3) >> 2;
+    __syncthreads();  // the previous tile's rows and dPre copy-out are done with sv
+    // V by LDS-DMA: wave instruction p moves chunks 64p .. 64p + 63 (1 KB) into sv + 256p words
+    int tail = -1;
+    for (int p = wave; p * 64 < nch; p += NT / 64) {
+      const int c = p * 64 + lane;
+      const long long gw = wa + 4LL * c;
+      const bool whole = c < nch && gw + 4 <= totw;
+      if (c < nch && !whole) tail = c;
+      __builtin_amdgcn_global_load_lds(whole ? (const void*)(Vw + gw) : (const void*)g_attn_zero,
+                                       (attn_lds_void*)(sv + 256 * p), 16, 0, 0);
+    }
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    if (tail >= 0) {  // the buffer's last chunk, partly past its end: the valid words by plain loads
+      const long long gw = wa + 4LL * tail;
+      for (int q = 0; q < 4 && gw + q < totw; ++q) sv[4 * tail + q] = Vw[gw + q];
+    }
+    __syncthreads();
+#pragma unroll
+    for (int s = 0; s < RPQ; ++s) {
+      const int r = qd + NQ * s;
+      if (r < nr) {  // quad-uniform
+        const int row = r0 + r;
+        unsigned* v = VF ? sdp + r * EP + j : sv + off + r * EP + j;  // (VF: the dPre pairs' LDS words)
+        float vxs[NWL], vys[NWL];
+        if constexpr (VF) {
+          const float2* vf = reinterpret_cast<const float2*>(sv + off + r * E) + j;
+#pragma unroll
+          for (int i = 0; i < NWL; ++i) {
+            const float2 p = (j + 4 * i < EP) ? vf[4 * i] : make_float2(0.f, 0.f);
+            vxs[i] = p.x;
+            vys[i] = p.y;
+          }
+        } else {
+#pragma unroll
+          for (int i = 0; i < NWL; ++i) {
+            const unsigned w = (j + 4 * i < EP) ? v[4 * i] : 0u;
+            vxs[i] = __uint_as_float(w << 16);
+            vys[i] = __uint_as_float(w & 0xFFFF0000u);
+          }
+        }
+        float lg[K][NC];
+#pragma unroll
+        for (int k = 0; k < K; ++k)
+#pragma unroll
+          for (int c = 0; c < NC; ++c) lg[k][c] = 0.f;
+#pragma unroll
+        for (int i = 0; i < NWL; ++i) {
+          const float vx = vxs[i], vy = vys[i];
+#pragma unroll
+          for (int k = 0; k < K; ++k)
+#pragma unroll
+            for (int c = 0; c < NC; ++c) {
+              lg[k][c] = fmaf(vx, qv[k][c][i][0], lg[k][c]);
+              lg[k][c] = fmaf(vy, qv[k][c][i][1], lg[k][c]);
+            }
+        }
+#pragma unroll
+        for (int k = 0; k < K; ++k)
+#pragma unroll
+          for (int c = 0; c < NC; ++c) {
+            lg[k][c] += quad_xor1(lg[k][c]);
+            lg[k][c] += quad_xor2(lg[k][c]);
+          }
+        float dl[K][NC];  // dL/dlogit (GRAD)
+        if constexpr (!CRM) {
+          const float x = xr[s][0];
+          float m[K], y[K], msum = 0.f;
+#pragma unroll
+          for (int k = 0; k < K; ++k) {
+            m[k] = sigmoidf_(lg[k][0]);
+            msum += m[k];
+            y[k] = yr[s][k][0];
+          }
+#pragma unroll
+          for (int k = 0; k < K; ++k)
+#pragma unroll
+            for (int jj = 0; jj < K; ++jj) {
+              const float dd = m[k] * x - y[jj];
+              cost[k * K + jj] = fmaf(dd, dd, cost[k * K + jj]);
+            }
+          const float ds = msum - 1.0f;
+          cost[K * K] = fmaf(ds, ds, cost[K * K]);
+          if ((a.mask_out || a.pred_out) && j == 0) {
+#pragma unroll
+            for (int k = 0; k < K; ++k) {
+              const long long o = ((long long)b * K + k) * a.rows_per_b + row;
+              if (a.mask_out) a.mask_out[o] = m[k];
+              if (a.pred_out) a.pred_out[o] = m[k] * x;
+            }
+          }
+          if constexpr (GRAD) {
+#pragma unroll
+            for (int k = 0; k < K; ++k) {
+              float yp = y[0];
+#pragma unroll
+              for (int jj = 1; jj < K; ++jj) yp = pm[k] == jj ? y[jj] : yp;
+              dl[k][0] = mag_dl<ADV>(a, k, m, x, yp, ds, ADV ? ge[ADV ? s : 0][ADV ? k : 0] : 0.f);
+            }
+          }
+        } else {
+          const float2 x = make_float2(xr[s][0], xr[s][1]);
+          float2 p[K];
+#pragma unroll
+          for (int k = 0; k < K; ++k) {
+            // cRM_EvalVer.py:269 (10 tanh) and :688 (inverse compression), fp32 as the reference
+            const float mcr = 10.f * tanhf(lg[k][0]);
+            const float mci = 10.f * tanhf(lg[k][1]);
+            const float mr = -10.f * logf((10.f - mcr) / (10.f + mcr));
+            const float mi = -10.f * logf((10.f - mci) / (10.f + mci));
+            p[k] = make_float2(mr * x.x - mi * x.y, mr * x.y + mi * x.x);
+            if (j == 0) {
+              const long long o = 2 * (((long long)b * K + k) * a.rows_per_b + row);
+              if (a.mask_out) { a.mask_out[o] = mr; a.mask_out[o + 1] = mi; }
+              if (a.pred_out) { a.pred_out[o] = p[k].x; a.pred_out[o + 1] = p[k].y; }
+            }
+            if constexpr (GRAD) {
+              // d(M)/d(logit) through the same fp32 chain: dM/dMc * dMc/dl
+              const float dmc_r = 10.f * (1.f / (10.f - mcr) + 1.f / (10.f + mcr));
+              const float dmc_i = 10.f * (1.f / (10.f - mci) + 1.f / (10.f + mci));
+              dl[k][0] = dmc_r * (10.f * (1.f - (mcr * 0.1f) * (mcr * 0.1f)));
+              dl[k][1] = dmc_i * (10.f * (1.f - (mci * 0.1f) * (mci * 0.1f)));
+            }
+          }
+#pragma unroll
+          for (int k = 0; k < K; ++k)
+#pragma unroll
+            for (int jj = 0; jj < K; ++jj) {
+              const float dr = p[k].x - yr[s][jj][0], di = p[k].y - yr[s][jj][1];
+              cost[k * K + jj] = fmaf(dr, dr, fmaf(di, di, cost[k * K + jj]));
+            }
+          if constexpr (GRAD) {
+#pragma unroll
+            for (int k = 0; k < K; ++k) {
+              float2 yp = make_float2(yr[s][0][0], yr[s][0][1]);
+#pragma unroll
+              for (int jj = 1; jj < K; ++jj) yp = pm[k] == jj ? make_float2(yr[s][jj][0], yr[s][jj][1]) : yp;
+              const float gr = 2.f * a.s1 * (p[k].x - yp.x), gi = 2.f * a.s1 * (p[k].y - yp.y);
+              // P = M (x) X: dMr = gr xr + gi xi ; dMi = -gr xi + gi xr
+              dl[k][0] *= gr * x.x + gi * x.y;
+              dl[k][1] *= -gr * x.y + gi * x.x;
+            }
+          }
+        }
+        if constexpr (GRAD) {
+          // dV[e] = sum_{k,c} dl_kc q_kc[e]; dPre = dV (1 - V^2) as bf16 over the lane's own words;
+          // dq_kc[e] += dl_kc V[e]
+#pragma unroll
+          for (int i = 0; i < NWL; ++i) {
+            const float vx = vxs[i], vy = vys[i];
+            float g0 = 0.f, g1 = 0.f;
+#pragma unroll
+            for (int k = 0; k < K; ++k)
+#pragma unroll
+              for (int c = 0; c < NC; ++c) {
+                g0 = fmaf(dl[k][c], qv[k][c][i][0], g0);
+                g1 = fmaf(dl[k][c], qv[k][c][i][1], g1);
+                dq[k][c][i][0] = fmaf(dl[k][c], vx, dq[k][c][i][0]);
+                dq[k][c][i][1] = fmaf(dl[k][c], vy, dq[k][c][i][1]);
+              }
+            __hip_bfloat162 o2 = __float22bfloat162_rn(make_float2(g0 * (1.f - vx * vx), g1 * (1.f - vy * vy)));
+            if (j + 4 * i < EP) v[4 * i] = *reinterpret_cast<unsigned*>(&o2);
+          }
+        }
+      }
+    }
+    if constexpr (GRAD) {
+      // the tile's dPre words, ready as bf16 pairs in LDS (four LDS words per 16-B store: only 4-B aligned)
+      __syncthreads();
+      const unsigned* so = VF ? sdp : sv + off;
+      store_dpre_bf16<EP>(a.dPreB, a.ldpb, b, a.T, a.F, r0, nr, [so](int i) { return so[i]; });
+    }
+  }
+
+  // ---- block reductions (fixed order: lane trees, then waves 0..3); costs from lane 0 of each quad
+  __syncthreads();
+  if constexpr (GRAD) {
+#pragma unroll
+    for (int k = 0; k < K; ++k)
+#pragma unroll
+      for (int c = 0; c < NC; ++c)
+#pragma unroll
+        for (int i = 0; i < NWL; ++i)
+#pragma unroll
+          for (int h = 0; h < 2; ++h) {
+            float s = dq[k][c][i][h];
+#pragma unroll
+            for (int o = 4; o < 64; o <<= 1) s += __shfl_xor(s, o, 64);
+            const int w = lane + 4 * i;  // lanes 0..3 hold the wave's sums of pairs j + 4i
+            if (lane < 4 && w < EP) sdq[(wave * K + k) * QW + c * E + 2 * w + h] = s;
+          }
+  }
+  // (its barrier also publishes sdq)
+  reduce_costs(cost, j == 0, a.part_loss + ((long long)b * a.nblk + blockIdx.x) * (K * K + 1));
+  if constexpr (GRAD) {
+    float* pd = a.part_dq + ((long long)b * a.nblk + blockIdx.x) * K * QW;
+    for (int i = tid; i < K * QW; i += NT)
+      pd[i] = sdq[0 * K * QW + i] + sdq[1 * K * QW + i] + sdq[2 * K * QW + i] + sdq[3 * K * QW + i];
+  }
 }
 
 // PIT selection: per utterance, lowest-index permutation minimising sum_k C[k][perm k].  One
@@ -237,50 +713,31 @@ __global__ __launch_bounds__(256) void finalize_kernel(const float* __restrict__
   }
 }
 
+int launch_rows(void (*kern)(AttnArgs), const AttnArgs& a, hipStream_t st) {
+  hipLaunchKernelGGL(kern, dim3(a.nblk, a.B), dim3(NT), 0, st, a);
+  DL4SS_CHECK_LAUNCH();
+  return 0;
+}
+
+// a.gext (the adversarial GRAD pass; magnitude only, attn_common) picks the ADV form of the same kernel
 template <int E, int K, bool CRM, bool VB>
 int launch_attn(bool grad, const AttnArgs& a, hipStream_t st) {
-  dim3 grid(a.nblk, a.B);
   if constexpr (!(CRM && K == 3)) {  // the throughput steps' path (16-B aligned V; bf16 dPre), magnitude and
                                      // cRM (K = 3 cRM: the quad kernel's 2 x 3 query halves spill; attn_kernel)
     // fp32 V or cRM: only for a bf16-dPre caller (which passes dPre_bf16 to its COST pass too, so both
     // passes of a PIT step sum the logits alike); the fp32 parity step keeps attn_kernel
     const bool q4 = (VB && !CRM) ? (a.dPreB || !grad) : a.dPreB != nullptr;
     if (q4 && ((uintptr_t)(VB ? (const void*)a.Vb : (const void*)a.V) & 15) == 0) {
-      if (grad)
-        hipLaunchKernelGGL((attn_q4_kernel<E, K, true, !VB, CRM>), grid, dim3(NT), 0, st, a);
-      else
-        hipLaunchKernelGGL((attn_q4_kernel<E, K, false, !VB, CRM>), grid, dim3(NT), 0, st, a);
-      DL4SS_CHECK_LAUNCH();
-      return 0;
+      if constexpr (!CRM)
+        if (a.gext) return launch_rows(attn_q4_kernel<E, K, true, !VB, false, true>, a, st);
+      return grad ? launch_rows(attn_q4_kernel<E, K, true, !VB, CRM>, a, st)
+                  : launch_rows(attn_q4_kernel<E, K, false, !VB, CRM>, a, st);
     }
   }
-  if (grad)
-    hipLaunchKernelGGL((attn_kernel<E, K, CRM, true, VB>), grid, dim3(NT), 0, st, a);
-  else
-    hipLaunchKernelGGL((attn_kernel<E, K, CRM, false, VB>), grid, dim3(NT), 0, st, a);
-  DL4SS_CHECK_LAUNCH();
-  return 0;
-}
-
-// the adversarial GRAD pass: the kernel form launch_attn picks for the same arguments, with gext
-template <int E, int K, bool VB>
-int launch_attn_adv(const AttnArgs& a, const float* gext, hipStream_t st) {
-  dim3 grid(a.nblk, a.B);
-  if (a.dPreB && ((uintptr_t)(VB ? (const void*)a.Vb : (const void*)a.V) & 15) == 0)
-    hipLaunchKernelGGL((attn_q4_adv_kernel<E, K, !VB>), grid, dim3(NT), 0, st, a, gext);
-  else
-    hipLaunchKernelGGL((attn_adv_kernel<E, K, VB>), grid, dim3(NT), 0, st, a, gext);
-  DL4SS_CHECK_LAUNCH();
-  return 0;
-}
-
-template <bool VB>
-int dispatch_adv(int E, int K, const AttnArgs& a, const float* gext, hipStream_t st) {
-  if (E != 50) return (int)hipErrorInvalidValue;
-  if (K == 1) return launch_attn_adv<50, 1, VB>(a, gext, st);
-  if (K == 2) return launch_attn_adv<50, 2, VB>(a, gext, st);
-  if (K == 3) return launch_attn_adv<50, 3, VB>(a, gext, st);
-  return (int)hipErrorInvalidValue;
+  if constexpr (!CRM)
+    if (a.gext) return launch_rows(attn_kernel<E, K, false, true, VB, true>, a, st);
+  return grad ? launch_rows(attn_kernel<E, K, CRM, true, VB>, a, st)
+              : launch_rows(attn_kernel<E, K, CRM, false, VB>, a, st);
 }
 
 template <bool VB>
@@ -313,24 +770,13 @@ int attn_common(int pass, int crm, int B, int K, int T, int F, int E, const floa
   a.q = q; a.X = X; a.xs = x_bstride; a.Y = Y; a.ys = y_bstride; a.yks = y_kstride;
   a.perm = perm; a.s1 = s1; a.s2 = s2; a.dPre = dPre; a.part_loss = part_loss; a.part_dq = part_dq;
   a.dPreB = reinterpret_cast<unsigned*>(dPre_bf16); a.ldpb = dpre_bf16_ld;
-  a.mask_out = mask_out; a.pred_out = pred_out;
-  if (gext)
-    return Vb ? dispatch_adv<true>(E, K, a, gext, as_stream(stream))
-              : dispatch_adv<false>(E, K, a, gext, as_stream(stream));
+  a.mask_out = mask_out; a.pred_out = pred_out; a.gext = gext;
   return Vb ? dispatch_v<true>(E, K, crm, pass == 1, a, as_stream(stream))
             : dispatch_v<false>(E, K, crm, pass == 1, a, as_stream(stream));
 }
 }  // namespace
 
-DL4SS_API int dl4ss_attn_nblk(int T, int F) {
-  // 4 tiles per block: with attn_q4_kernel at C2 -- 32 x 32 blocks, one round at 4 resident per CU --
-  // GRAD 65.8 / 66.7 / 71.1 us at 4 / 2 / 3 tiles, COST + PIT select 25.2 / 25.8 / 27.1 us
-  // (profiles/r03_attn_q4.jsonl; round 2's attn_kernel preferred 3)
-  constexpr int tpb = 4;
-  const int rows = T * F;
-  int nblk = (rows + tpb * TILE - 1) / (tpb * TILE);
-  return nblk < 1 ? 1 : nblk;
-}
+DL4SS_API int dl4ss_attn_nblk(int T, int F) { return attn_tile::nblk((long long)T * F); }
 
 // pass: 0 = COST (costs / masks only), 1 = GRAD (costs + dPre + dq partials)
 DL4SS_API int dl4ss_mask_attn_loss(int pass, int crm, int B, int K, int T, int F, int E, const float* V,

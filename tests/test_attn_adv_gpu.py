@@ -1,7 +1,7 @@
 """The adversarial form of the magnitude GRAD pass (dl4ss_mask_attn_loss_adv, dl4ss_mask_attn_loss_adv_bf16v)
 and the adversarial step's loss-head kernel (dl4ss_disc_adv_heads) against fp64.
 
-GRAD pass: the three kernel forms -- attn_adv_kernel (fp32 V, fp32 dPre), attn_q4_adv_kernel on bf16 V and on
+GRAD pass: the three kernel forms -- attn_kernel's ADV form (fp32 V, fp32 dPre), attn_q4_kernel's on bf16 V and on
 fp32 V with bf16 dPre -- for K = 1..3 on the shapes of test_attn_gpu.py (ragged 256-row tiles, a V buffer that
 is no multiple of 16 B, dPre rows that do not start 16-B aligned).  The reference is the fp64 gradient of
     s1 sum (pred - Y_perm)^2 + s2 sum (sum_k m - 1)^2 + sum gext pred,   pred = m |X|, m = sigmoid(V . q)
